@@ -14,8 +14,16 @@ value = solves processed by all ranks / max-over-ranks wall time of the K steps.
 
 Protocol of the timed region: `--warmup` untimed steps, barrier + synchronize, EXACTLY `--steps` launches bracketed by one HIP event
 pair on the launch stream, synchronize, barrier.  Before the warm-up steps a DISCLOSED, untimed clock warm ("clock_warm_ms") keeps the
-GPU busy so that a short run is not timed on a clock still ramping up from idle.  A second, diagnostic pass of K launches with one
-event every 4 launches gives the per-launch distribution ("launch_us_median"); it is not part of `value`.
+GPU busy so that a short run is not timed on a clock still ramping up from idle.
+
+A plain run does only that: set up, warm up, time the K steps, write the outputs (--dump-outputs) and print the line.  Everything else
+the line can carry runs only with --full: a second, diagnostic pass of K launches with one event every 4 launches that gives the
+per-launch distribution ("launch_us_median"), the other scaling mode (N > 1), the copy-bandwidth ceiling, the end-to-end host path,
+BASELINE.json's other configs ("other_configs"), and the CPU baseline with its oracle spot check of the GPU result.  None of it is `value`.
+
+--dump-outputs DIR writes what the caller of the timed path received from its last step: DIR/df_du.npy (float32, (batch, 2 n^2);
+DIR/df_du_rank<r>.npy per rank when N > 1), a fixed seeded sample of rows if the whole would exceed 64 MB.  The inputs depend only on
+the arguments, so two builds can be compared output for output.
 """
 import argparse
 import gc
@@ -38,6 +46,7 @@ FLOPS_PER_SOLVE_REFERENCE = 53e3   # static estimate of the R
 N_SIMDS = 1024                 # 256 CUs x 4 SIMDs
 CLOCK_GHZ = 2.4                # MI355X_MICROARCH.md: max clock
 PMC_FILE = os.path.join("profiles", "pmc_counters.json")   # per-launch counters of the headline kernel from committed rocprofv3 --pmc passes
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs: at most this much in all (a seeded sample of rows beyond it)
 
 
 def make_inputs(n, N, seed=0):
@@ -58,6 +67,15 @@ def rank_inputs(n, N, world, rank, scaling):
         k0, k1 = shard_range(N, world, rank)
         return make_inputs(n, N, seed=0)[k0:k1]
     return make_inputs(n, N, seed=rank)
+
+
+def dump_outputs(out_dir, name, a, limit_bytes):
+    """Saves `a` as out_dir/<name>.npy; beyond limit_bytes a fixed seeded sample of its rows (in their original order)."""
+    os.makedirs(out_dir, exist_ok=True)
+    rows = max(1, limit_bytes // max(1, a[:1].nbytes))
+    if a.shape[0] > rows:
+        a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], rows, replace=False))]
+    np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def _timed_rate(fn, nsolves, budget_s, max_reps=100000):
@@ -239,8 +257,13 @@ def main():
     ap.add_argument("--scaling", choices=("strong", "weak"), default="strong",
                     help="strong (default): one global batch of --batch solves cut into contiguous per-GPU ranges; weak: --batch solves per GPU")
     ap.add_argument("--clock-warm-ms", type=float, default=50.0, help="untimed, disclosed GPU clock warm before the warm-up steps (0 = off)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the copy-bandwidth, end-to-end and second-scaling-mode measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the diagnostics: per-launch distribution pass, other scaling mode, copy bandwidth, end-to-end host path, "
+                         "other configs, CPU baseline + oracle spot check (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float32; at most 64 MB, a seeded sample of rows beyond it)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the oracle spot check")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the copy-bandwidth, end-to-end, other-config and second-scaling-mode measurements")
     ap.add_argument("--threads", type=int, default=0, help="threads per block override (0 = library default)")
     ap.add_argument("--blocks", type=int, default=0, help="blocks override (0 = one lane-group batch per block)")
     ap.add_argument("--build-dir", default=None, help="load the robot library from another build directory (tuning experiments)")
@@ -294,8 +317,9 @@ def main():
             dist.barrier()
             torch.cuda.synchronize(dev)
 
-    def run_mode(scaling, steps, warmup, clock_warm_ms):
-        """One complete measurement in one scaling mode; returns a dict of this job's numbers (rank 0's view after the MAX-reduce)."""
+    def run_mode(scaling, steps, warmup, clock_warm_ms, diagnostics, keep_out=False):
+        """One complete measurement in one scaling mode; returns a dict of this job's numbers (rank 0's view after the MAX-reduce).
+        diagnostics: also the per-launch distribution pass (--full); keep_out: a host copy of what the last timed step wrote."""
         x = rank_inputs(n, B, world, rank, scaling)   # strong: this rank's contiguous slice of the ONE global batch
         N = x.shape[0]
         d_in = torch.from_numpy(np.ascontiguousarray(x)).to(dev)
@@ -335,32 +359,37 @@ def main():
         fastest = elapsed
         if distributed:
             fastest, elapsed = reduce_min_max(elapsed, dist, red_dev)  # job time = slowest rank (all ranks started together behind the opening barrier)
-        # ---- diagnostic pass (not part of `value`): an event every CHUNK launches -> distribution of the per-launch time.  (An event after
-        # every single launch puts a marker packet between the kernels that costs ~3 us, more than a third of the kernel itself.)
-        CHUNK = 4
-        nch = max(1, steps // CHUNK)
-        evs = [torch.cuda.Event(enable_timing=True) for _ in range(nch + 1)]
-        evs[0].record(stream)
-        for i in range(nch):
-            for _ in range(CHUNK):
-                step()
-            evs[i + 1].record(stream)
-        torch.cuda.synchronize(dev)
-        per = np.array([evs[i].elapsed_time(evs[i + 1]) for i in range(nch)]) * 1e3 / CHUNK  # us per launch, chunk means
-        barrier()
+        out = d_out[:N].cpu().numpy() if keep_out else None
+        per = None
+        if diagnostics:
+            # ---- diagnostic pass (not part of `value`): an event every CHUNK launches -> distribution of the per-launch time.  (An event after
+            # every single launch puts a marker packet between the kernels that costs ~3 us, more than a third of the kernel itself.)
+            CHUNK = 4
+            nch = max(1, steps // CHUNK)
+            evs = [torch.cuda.Event(enable_timing=True) for _ in range(nch + 1)]
+            evs[0].record(stream)
+            for i in range(nch):
+                for _ in range(CHUNK):
+                    step()
+                evs[i + 1].record(stream)
+            torch.cuda.synchronize(dev)
+            per = np.array([evs[i].elapsed_time(evs[i + 1]) for i in range(nch)]) * 1e3 / CHUNK  # us per launch, chunk means
+            barrier()
         total = (B if scaling == "strong" else world * B) * steps
-        return {"x": x, "d_out": d_out, "N": N, "elapsed": elapsed, "fastest": fastest, "gpu_ms": gpu_ms, "per_launch_us": per, "solves": total,
+        return {"x": x, "d_out": d_out, "out": out, "N": N, "elapsed": elapsed, "fastest": fastest, "gpu_ms": gpu_ms, "per_launch_us": per, "solves": total,
                 "warm_launches": warm_launches}
 
     scaling = args.scaling
-    r = run_mode(scaling, args.steps, args.warmup, args.clock_warm_ms)
+    r = run_mode(scaling, args.steps, args.warmup, args.clock_warm_ms, args.full, keep_out=bool(args.dump_outputs))
+    if args.dump_outputs:  # what the caller of the timed path received from its last step
+        dump_outputs(args.dump_outputs, "df_du" if world == 1 else "df_du_rank%d" % rank, r["out"], DUMP_LIMIT_BYTES // world)
     if args.dump:
         os.makedirs(args.dump, exist_ok=True)
         np.save(os.path.join(args.dump, "out_rank%d.npy" % rank), r["d_out"][:r["N"]].cpu().numpy())
     other = None
-    if world > 1 and not args.no_extras:  # the other scaling mode as a second key (same protocol, clocks already warm)
+    if args.full and world > 1 and not args.no_extras:  # the other scaling mode as a second key (same protocol, clocks already warm)
         other_mode = "weak" if scaling == "strong" else "strong"
-        o = run_mode(other_mode, args.steps, args.warmup, 0.0)
+        o = run_mode(other_mode, args.steps, args.warmup, 0.0, True)
         other = {"scaling": other_mode, "value": o["solves"] / o["elapsed"], "unit": "solves/s", "ms_per_step": 1e3 * o["elapsed"] / args.steps,
                  "batch_per_gpu": o["N"], "global_batch": B if other_mode == "strong" else world * B}
 
@@ -399,8 +428,6 @@ def main():
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                          "traffic": traffic, "traffic_source": (PMC_FILE + " (rocprofv3 --pmc passes of this kernel build, not measured in this run)") if traffic else None,
                          "kernel": "forward_dynamics_gradient_kernel<float>", "launch_us": 1e3 * launch_ms,
-                         "launch_us_median": float(np.median(per)), "launch_us_min": float(per.min()), "launch_us_max": float(per.max()),
-                         "launch_us_note": "launch_us = event pair around the K timed launches / K; median/min/max = separate diagnostic pass, one event every 4 launches (span / 4; a marker after every launch costs ~3 us)",
                          "algorithmic_bytes_per_launch": bytes_per_solve * N,
                          "note": "the path is fp32-VALU bound (AI ~110 flop/B): see valu_issue_frac"},
             # solves/s x the REFERENCE's 53 kflop per solve / peak fp32: a reference-equivalent rate, NOT the utilisation of this kernel
@@ -409,9 +436,12 @@ def main():
             "valu_issue_frac": (valu_insts * 2.0 / (N_SIMDS * launch_ms * 1e-3 * CLOCK_GHZ * 1e9)) if valu_insts else None,
             "valu_issue_frac_source": (PMC_FILE + ": sq_insts_valu_per_launch x 2 cycles / (1024 SIMDs x launch_us x 2.4 GHz)") if valu_insts else None,
         }
+        if per is not None:
+            line["roofline"].update({"launch_us_median": float(np.median(per)), "launch_us_min": float(per.min()), "launch_us_max": float(per.max()),
+                                     "launch_us_note": "launch_us = event pair around the K timed launches / K; median/min/max = separate diagnostic pass, one event every 4 launches (span / 4; a marker after every launch costs ~3 us)"})
         if other is not None:
             line["other_scaling"] = other
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             line["copy_bw_measured_GBps"] = measured_copy_bandwidth(torch, dev)
             line["roofline"]["frac_of_measured_copy_bw"] = achieved / line["copy_bw_measured_GBps"]
             # end-to-end incl. H2D/D2H through the host-buffer C-ABI entry point (pageable NumPy memory); never `value`
@@ -434,12 +464,12 @@ def main():
             line["end_to_end_pinned_note"] = "same call, caller's buffers from grid_host_alloc (page-locked): chunked H2D | kernel | D2H pipeline; the %.1f MB D2H at PCIe rate is the floor" % (xh.shape[0] * 2 * n * n * 4 / 1e6)
             assert np.array_equal(op, lib.forward_dynamics_gradient_host(xh))
             del xp, op
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             try:  # (diagnostics: a failure here must not cost the headline line)
                 line["other_configs"] = other_configs(torch)
             except Exception as exc:
                 line["other_configs"] = {"error": repr(exc)}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             # the only place the oracle (test infrastructure) is touched: the CPU baseline leg, which also spot-checks the GPU result
             line["cpu_baseline"] = cpu_baseline(robot, r["x"])
             from oracle.rbd_oracle import Oracle
@@ -449,7 +479,7 @@ def main():
             err = float(max(np.abs(got[k] - ref[k]).max() / np.abs(ref[k]).max() for k in range(32)))
             assert args.no_parity or err <= 1e-4, "parity check failed: %g" % err
             line["cpu_baseline"]["gpu_parity_max_rel_err_vs_fp64_oracle"] = err
-        elif not args.no_cpu_baseline:
+        elif args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = None
         print(json.dumps(line))
     if distributed:

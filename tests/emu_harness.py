@@ -1,6 +1,8 @@
 """Builds the CPU *emulation* of a robot library: the unchanged generated header + the unchanged C-ABI shim compiled by
 g++ against tests/emu/hip/hip_runtime.h (threads-per-lane emulation).  Test infrastructure only."""
+import atexit
 import os
+import shutil
 import subprocess
 import tempfile
 
@@ -12,6 +14,16 @@ EMU_INC = os.path.join(HERE, "emu")
 MANIFEST = os.path.join(EMU_INC, "prebuild_manifest.json")
 _CACHE = {}
 _REQUESTED = {}  # key -> manifest entry of every library this process asked for (pytest --update-emu-manifest writes them out)
+_BUILD_ROOT = None
+
+
+def _build_root():
+    """This process's own build directory, removed at exit: a shared fixed path would collide with another run or another user's files."""
+    global _BUILD_ROOT
+    if _BUILD_ROOT is None:
+        _BUILD_ROOT = tempfile.mkdtemp(prefix="grid_emu_build_")
+        atexit.register(shutil.rmtree, _BUILD_ROOT, True)
+    return _BUILD_ROOT
 
 
 def _key(robot, cols_per_lane, tuning, debug_mode):
@@ -19,7 +31,7 @@ def _key(robot, cols_per_lane, tuning, debug_mode):
 
 
 def _build(robot, key, cols_per_lane, tuning, debug_mode):
-    out_dir = os.path.join(tempfile.gettempdir(), "grid_emu_build", key)
+    out_dir = os.path.join(_build_root(), key)
     generate_header(robot, out_dir, cols_per_lane=cols_per_lane, tuning=tuning, debug_mode=debug_mode)
     so = os.path.join(out_dir, "libgrid_emu_%s.so" % key)
     cmd = ["g++", "-std=c++20", "-O0", "-g0", "-fno-gnu-unique",  # (no process-wide "unique" symbols: inline variables and function-local statics stay private to each robot library)
@@ -50,6 +62,7 @@ def prebuild_from_manifest(workers):
     if not os.path.exists(MANIFEST):
         return 0
     entries = [e for e in json.load(open(MANIFEST))]
+    _build_root()  # (created before the fork: the workers build into the parent's directory)
     # (worker PROCESSES: the generator writes its header through module-level state, two generations in one process would mix)
     with mp.get_context("fork").Pool(workers) as pool:
         done = [r for r in pool.map(_prebuild_one, entries, chunksize=1) if r is not None]

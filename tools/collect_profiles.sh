@@ -5,7 +5,7 @@
 # stats + counters of the secondary configurations (ONE batch size per output directory: 30-DoF humanoid @16384, quadruped @4096,
 # second order on the 7-DoF arm @65536).
 O=${1:-gpurun_out/prof}; mkdir -p $O; export TMPDIR=/tmp
-B="python3 bench.py --gpus 1 --steps 20 --warmup 5"
+B="python3 bench.py --gpus 1 --steps 20 --warmup 5 --full"
 $B > $O/bench.json 2> $O/bench.err || exit 1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- $B --no-cpu-baseline --no-extras --no-parity > $O/bench_under_rocprof.json 2> $O/trace.err || exit 1
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -o run -- $B --no-cpu-baseline --no-extras --no-parity --clock-warm-ms 0 > /dev/null 2> $O/pmc_fetch.err || exit 1

@@ -47,9 +47,9 @@ json.dump({"kernel": "forward_dynamics_gradient_kernel<float>", "robot": "iiwa14
            "sq_insts_valu_per_launch": out["SQ_INSTS_VALU"], "sq_wave_cycles_per_launch": out["SQ_WAVE_CYCLES"],
            "correction": "MI355X_MICROARCH.md HBM section: FETCH_SIZE reports 1/2 of streamed read bytes on gfx950 (x2 applied; dword-wide reads are uncalibrated), WRITE_SIZE exact for 16-byte stores; units KB",
            "algorithmic_bytes_per_launch": alg,
-           "source": "%s build: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE / SQ_* (separate passes) around `python3 bench.py --gpus 1 --steps 20 --warmup 5` (tools/collect_profiles.sh); profiles/%s_pmc_sq.txt" % (tag, tag)},
+           "source": "%s build: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE / SQ_* (separate passes) around `python3 bench.py --gpus 1 --steps 20 --warmup 5 --full` (tools/collect_profiles.sh); profiles/%s_pmc_sq.txt" % (tag, tag)},
           open(os.path.join(P, "pmc_counters.json"), "w"), indent=1)
-write_sq(os.path.join(P, tag + "_pmc_sq.txt"), "rocprofv3 --pmc <counters> --kernel-trace -- python3 bench.py --gpus 1 --steps 20 --warmup 5   (tools/collect_profiles.sh; per launch of 16384 iiwa14 solves = 2048 waves)", out)
+write_sq(os.path.join(P, tag + "_pmc_sq.txt"), "rocprofv3 --pmc <counters> --kernel-trace -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full   (tools/collect_profiles.sh; per launch of 16384 iiwa14 solves = 2048 waves)", out)
 for robot in ("atlas", "hyq"):
     fs = glob.glob(base + robot + "_trace/**/*kernel_stats.csv", recursive=True)
     if fs:
