@@ -143,8 +143,17 @@ class GRiDCodeGenerator:
         gen_branch_frame_plan, gen_branch_frame_constants, gen_branch_frame_library, gen_branch_frame_components, gen_forward_dynamics_gradient_inner_branch, gen_forward_dynamics_gradient_inner_branch_stream, \
         gen_forward_dynamics_gradient_inner_branch_function_call
 
+    # end-effector kinematics (reference algorithms/_eepose_gradient_hessian.py)
+    from .algorithms import gen_end_effector_pose_inner_temp_mem_size, gen_end_effector_pose_gradient_inner_temp_mem_size, \
+        gen_end_effector_pose_gradient_hessian_inner_temp_mem_size, gen_eepose_constants, gen_eepose_buffers, \
+        gen_end_effector_pose_inner, gen_end_effector_pose_device, gen_end_effector_pose_kernel, gen_end_effector_pose_host, \
+        gen_end_effector_pose_gradient_inner, gen_end_effector_pose_gradient_device, gen_end_effector_pose_gradient_kernel, gen_end_effector_pose_gradient_host, \
+        gen_end_effector_pose_gradient_hessian_inner, gen_end_effector_pose_gradient_hessian_device, gen_end_effector_pose_gradient_hessian_kernel, \
+        gen_end_effector_pose_gradient_hessian_host, gen_eepose_and_derivatives
+
     # NumPy debug helpers with the reference's names and signatures (reference GRiDCodeGenerator.py:50-51, README "Additional Features")
     from ._test import test_rnea, test_minv, test_rnea_grad, test_fd_grad
+    from ._test import test_end_effector_pose, test_end_effector_pose_gradient, test_end_effector_pose_hessian
 
     def __init__(self, robotObj, DEBUG_MODE=False, NEED_PRINT_MAT=False, USE_DYNAMIC_SHARED_MEM=True, FILE_NAMESPACE="grid", COLS_PER_LANE=None, tuning=None):
         if not USE_DYNAMIC_SHARED_MEM:
@@ -444,6 +453,8 @@ class GRiDCodeGenerator:
                                  "gpuErrchk(hipHostFree(hd_data->h_q_qd_u)); gpuErrchk(hipHostFree(hd_data->h_q_qd)); gpuErrchk(hipHostFree(hd_data->h_q));",
                                  "gpuErrchk(hipHostFree(hd_data->h_c)); gpuErrchk(hipHostFree(hd_data->h_Minv)); gpuErrchk(hipHostFree(hd_data->h_qdd));",
                                  "gpuErrchk(hipHostFree(hd_data->h_dc_du)); gpuErrchk(hipHostFree(hd_data->h_df_du));",
+                                 "// kinematics buffers: allocated by the first end_effector_pose* host call (grid_ee_reserve)",
+                                 "grid_ee_release(&hd_data->d_eePos, &hd_data->h_eePos); grid_ee_release(&hd_data->d_deePos, &hd_data->h_deePos); grid_ee_release(&hd_data->d_d2eePos, &hd_data->h_d2eePos);",
                                  "free(hd_data);",
                                  "for(int i=0; i<" + str(MAX_STREAMS) + "; i++){gpuErrchk(hipStreamDestroy(streams[i]));} free(streams);"])
         self.gen_add_end_function()
@@ -516,6 +527,8 @@ class GRiDCodeGenerator:
         self.gen_idsva_so(use_thread_group)
         self.gen_fdsva_so(use_thread_group)
         if not self.nested:
+            self.gen_eepose_and_derivatives(use_thread_group)  # (outer namespace only: the nested `wide` instance carries the second-order kernels alone)
+        if not self.nested:
             self.gen_init_close_grid()
 
     # ------------------------------------------------------------------ everything
@@ -565,6 +578,18 @@ class GRiDCodeGenerator:
                       "    __global__ fdsva_so_kernel<T>(T *d_df2, const T *d_q_qd_u, const int stride_q_qd_u, const robotModel<T> *d_robotModel, const T gravity, const int NUM_TIMESTEPS)",
                       "    __host__   fdsva_so<T>(gridData<T> *hd_data, const robotModel<T> *d_robotModel, const T gravity, const int num_timesteps, const dim3 block_dimms, const dim3 thread_dimms, hipStream_t *streams)",
                       ""] if self.gen_idsva_so_available() else []) + [
+                      "    end-effector kinematics (every leaf joint is an end effector, NUM_EES of them; eePos[k*6E + 6e + c], deePos[k*6En + 6(e n + j) + c],",
+                      "    d2eePos[k*6En^2 + e*6n^2 + c*n^2 + i*n + j]; the host wrappers allocate hd_data's kinematics buffers on first use):",
+                      "    __device__ end_effector_pose_device<T>(T *s_eePos, const T *s_q, T *s_work, const robotModel<T> *d_robotModel, const int lane)",
+                      "    __global__ end_effector_pose_kernel<T>(T *d_eePos, const T *d_q, const int stride_q, const robotModel<T> *d_robotModel, const int NUM_TIMESTEPS)",
+                      "    __host__   end_effector_pose<T,USE_COMPRESSED_MEM=false>(gridData<T> *hd_data, const robotModel<T> *d_robotModel, const int num_timesteps, const dim3 block_dimms, const dim3 thread_dimms, hipStream_t *streams)",
+                      "    __device__ end_effector_pose_gradient_device<T>(T *s_deePos, const T *s_q, T *s_work, const robotModel<T> *d_robotModel, const int lane)",
+                      "    __global__ end_effector_pose_gradient_kernel<T>(T *d_deePos, const T *d_q, const int stride_q, const robotModel<T> *d_robotModel, const int NUM_TIMESTEPS)",
+                      "    __host__   end_effector_pose_gradient<T,USE_COMPRESSED_MEM=false>(gridData<T> *hd_data, const robotModel<T> *d_robotModel, const int num_timesteps, const dim3 block_dimms, const dim3 thread_dimms, hipStream_t *streams)",
+                      "    __device__ end_effector_pose_gradient_hessian_device<T>(T *d2, T *s_deePos, const T *s_q, T *s_work, const robotModel<T> *d_robotModel, const int lane, const bool active)",
+                      "    __global__ end_effector_pose_gradient_hessian_kernel<T>(T *d_d2eePos, T *d_deePos, const T *d_q, const int stride_q, const robotModel<T> *d_robotModel, const int NUM_TIMESTEPS)",
+                      "    __host__   end_effector_pose_gradient_hessian<T,USE_COMPRESSED_MEM=false>(gridData<T> *hd_data, const robotModel<T> *d_robotModel, const int num_timesteps, const dim3 block_dimms, const dim3 thread_dimms, hipStream_t *streams)",
+                      "",
                       "Every host function also exists as NAME_single_timing and NAME_compute_only (no streams argument).",
                       "",
                       "Execution model (differs from the CUDA original by design): a lane group of GRID_LANES_PER_SOLVE = " + str(self.lanes_per_solve) + " consecutive lanes of one",

@@ -138,3 +138,136 @@ def test_fd_grad(self, q, qd, u, GRAVITY=-9.81):
     Minv = test_minv(self, q, True)
     qdd = Minv @ (np.asarray(u) - c)
     return -Minv @ test_rnea_grad(self, q, qd, qdd, GRAVITY)
+
+
+# ---------------------------------------------------------------------------------------------------- end-effector kinematics
+# From the joint descriptions alone (xyz, rpy, axis, type of every joint; reference algorithms/_eepose_gradient_hessian.py): T_e(q) = T_root ... T_leaf with
+# T_j(q) = [R_tree_j Rot(axis_j, q) | xyz_j] (revolute) or [R_tree_j | xyz_j + R_tree_j axis_j q] (prismatic), pose [x, y, z, roll, pitch, yaw],
+# roll = atan2(R21, R22), pitch = -atan2(R20, sqrt(R21^2 + R22^2)), yaw = atan2(R10, R00).  The derivatives are analytic (products of the joint transforms
+# with their derivatives), so the tests can pin them against finite differences.  Layouts: (E, 6), (E, 6, n) and (E, 6, n, n).
+
+def _rpy_matrix(rpy):
+    r, p, y = rpy
+    cr, sr, cp, sp, cy, sy = np.cos(r), np.sin(r), np.cos(p), np.sin(p), np.cos(y), np.sin(y)
+    return np.array([[cy * cp, cy * sp * sr - sy * cr, cy * sp * cr + sy * sr],
+                     [sy * cp, sy * sp * sr + cy * cr, sy * sp * cr - cy * sr],
+                     [-sp, cp * sr, cp * cr]])
+
+
+def _ee_joints(self):
+    """(parent, xyz, R_tree, axis index, revolute) of every joint, from the robot's own joint descriptions"""
+    out = []
+    for jt in self.robot.get_joints_ordered_by_id():
+        out.append((int(jt.parent), np.asarray(jt.xyz, float), _rpy_matrix(jt.rpy), int(jt.axis), jt.jtype == "revolute"))
+    return out
+
+
+def _ee_local(J, q, order):
+    """4x4 homogeneous transform of one joint and its first and second derivative in q (order 0, 1, 2)"""
+    _, xyz, Rt, a, rev = J
+    T = np.zeros((4, 4))
+    if rev:
+        K = np.zeros((3, 3))
+        a1, a2 = (a + 1) % 3, (a + 2) % 3
+        K[a2, a1], K[a1, a2] = 1.0, -1.0  # skew(e_a)
+        c, s = np.cos(q), np.sin(q)
+        Rot = np.eye(3) + s * K + (1 - c) * K @ K
+        dRot = [Rot, c * K + s * K @ K, -s * K + c * K @ K][order]
+        T[:3, :3] = Rt @ dRot
+        if order == 0:
+            T[:3, 3] = xyz
+            T[3, 3] = 1.0
+    else:
+        if order == 0:
+            T[:3, :3] = Rt
+            T[:3, 3] = xyz + Rt[:, a] * q
+            T[3, 3] = 1.0
+        elif order == 1:
+            T[:3, 3] = Rt[:, a]
+    return T
+
+
+def _ee_leaves(self):
+    m = self.model
+    return [j for j in range(m.n) if not m.children[j]]
+
+
+def _ee_path(joints, leaf):
+    path = []
+    j = leaf
+    while j != -1:
+        path.append(j)
+        j = joints[j][0]
+    return path[::-1]
+
+
+def _ee_chain(joints, q, path, d):
+    """product over the root path with joint path[k] differentiated d[k] times"""
+    T = np.eye(4)
+    for k, j in enumerate(path):
+        T = T @ _ee_local(joints[j], float(q[j]), d.get(j, 0))
+    return T
+
+
+def _atan2_derivs(y, x, dy, dx, d2y=None, d2x=None):
+    """first (n) and second (n x n) derivatives of atan2(y, x) from those of y and x"""
+    D = x * x + y * y
+    g = (x * dy - y * dx) / D
+    if d2y is None:
+        return g
+    dD = 2 * (x * dx + y * dy)
+    H = (np.outer(dy, dx) + x * d2y - np.outer(dx, dy) - y * d2x) / D - np.outer(x * dy - y * dx, dD) / D ** 2
+    return g, H
+
+
+def _ee_all(self, q, order):
+    joints = _ee_joints(self)
+    n = len(joints)
+    q = np.asarray(q, float)
+    leaves = _ee_leaves(self)
+    E = len(leaves)
+    pose, grad, hess = np.zeros((E, 6)), np.zeros((E, 6, n)), np.zeros((E, 6, n, n))
+    for e, leaf in enumerate(leaves):
+        path = _ee_path(joints, leaf)
+        T = _ee_chain(joints, q, path, {})
+        dT = np.zeros((n, 4, 4))
+        d2T = np.zeros((n, n, 4, 4))
+        if order >= 1:
+            for i in path:
+                dT[i] = _ee_chain(joints, q, path, {i: 1})
+        if order >= 2:
+            for i in path:
+                for j in path:
+                    d2T[i, j] = _ee_chain(joints, q, path, {i: 2} if i == j else {i: 1, j: 1})
+        R, p = T[:3, :3], T[:3, 3]
+        s = np.hypot(R[2, 1], R[2, 2])
+        pose[e] = [p[0], p[1], p[2], np.arctan2(R[2, 1], R[2, 2]), -np.arctan2(R[2, 0], s), np.arctan2(R[1, 0], R[0, 0])]
+        if order == 0:
+            continue
+        el = lambda r, c: (dT[:, r, c], d2T[:, :, r, c])
+        (d21, h21), (d22, h22), (d20, h20), (d10, h10), (d00, h00) = el(2, 1), el(2, 2), el(2, 0), el(1, 0), el(0, 0)
+        ds = (R[2, 1] * d21 + R[2, 2] * d22) / s
+        h_s = (np.outer(d21, d21) + R[2, 1] * h21 + np.outer(d22, d22) + R[2, 2] * h22) / s - np.outer(ds, ds) / s
+        grad[e, :3] = dT[:, :3, 3].T
+        hess[e, :3] = np.moveaxis(d2T[:, :, :3, 3], 2, 0)
+        for c, (y, x, dy, dx, hy, hx, sign) in enumerate([(R[2, 1], R[2, 2], d21, d22, h21, h22, 1.0), (R[2, 0], s, d20, ds, h20, h_s, -1.0),
+                                                          (R[1, 0], R[0, 0], d10, d00, h10, h00, 1.0)]):
+            g, H = _atan2_derivs(y, x, dy, dx, hy, hx)
+            grad[e, 3 + c] = sign * g
+            hess[e, 3 + c] = sign * 0.5 * (H + H.T)
+    return pose, grad, hess
+
+
+def test_end_effector_pose(self, q):
+    """(E, 6): [x, y, z, roll, pitch, yaw] of every leaf joint (ascending id)"""
+    return _ee_all(self, q, 0)[0]
+
+
+def test_end_effector_pose_gradient(self, q):
+    """(E, 6, n): d pose / d q_j (0 for joints off the leaf's root path)"""
+    return _ee_all(self, q, 1)[1]
+
+
+def test_end_effector_pose_hessian(self, q):
+    """(E, 6, n, n): d2 pose / d q_i d q_j (symmetric; 0 unless both joints are on the leaf's root path)"""
+    return _ee_all(self, q, 2)[2]

@@ -34,6 +34,14 @@ struct grid_typed {
     grid::gridData<T> *hd_data = nullptr;
 };
 
+// staging of the kinematics host entry points (grid_end_effector_pose*_host): allocated by the first kinematics call on a handle, never by grid_init,
+// and grown when a later call needs more; capacities in elements of T
+template <typename T>
+struct ee_stage {
+    T *d_q = nullptr, *d_out = nullptr, *d_dee = nullptr;
+    size_t q_cap = 0, out_cap = 0, dee_cap = 0;
+};
+
 struct grid_handle {
     int device;
     int max_timesteps;
@@ -48,10 +56,16 @@ struct grid_handle {
     // (or threads) are made safe by ordering them: every launch waits for the previous one's event before it may touch the workspace
     hipEvent_t so_done = nullptr;
     bool so_pending = false;
+    ee_stage<float> ee32;
+    ee_stage<double> ee64;
 };
 template <typename T> static inline grid_typed<T> &typed(grid_handle *h);
 template <> inline grid_typed<float> &typed<float>(grid_handle *h) { return h->f32; }
 template <> inline grid_typed<double> &typed<double>(grid_handle *h) { return h->f64; }
+
+template <typename T> static inline ee_stage<T> &ee_staging(grid_handle *h);
+template <> inline ee_stage<float> &ee_staging<float>(grid_handle *h) { return h->ee32; }
+template <> inline ee_stage<double> &ee_staging<double>(grid_handle *h) { return h->ee64; }
 
 static thread_local char g_err[512] = "";
 
@@ -557,6 +571,91 @@ static int so_host(grid_handle *h, const T *h_q_qd_u, const T *h_qdd, int N, T g
 #endif
 }
 
+// ---------------------------------------------------------------------------------------------------------------- end-effector kinematics
+// which: 0 = pose (d_out = eePos, 6E per solve), 1 = gradient (deePos, 6En), 2 = Hessian (d2eePos, 6En^2; d_dee receives the gradient or is NULL)
+static const size_t EE_REC[3] = {(size_t)6 * grid::NUM_EES, (size_t)6 * grid::NUM_EES * grid::NUM_JOINTS, (size_t)6 * grid::NUM_EES * grid::NUM_JOINTS * grid::NUM_JOINTS};
+
+template <typename T>
+static int ee_device(grid_handle *h, const T *d_q, int stride, int N, T *d_out, T *d_dee, void *stream, int which) {
+    int rc = check_args(h, N);
+    if (rc) return rc;
+    if ((rc = check_io(d_q, stride, (int)grid::NUM_JOINTS, d_out, N))) return rc;
+    if (N == 0) return 0;
+    GRID_ON_DEVICE(h);
+    if ((rc = ensure_typed<T>(h))) return rc;
+    launch_cfg c;
+    const grid::robotModel<T> *rm = typed<T>(h).d_robotModel;
+    if (which == 0) {
+        if ((rc = make_launch<T>(h, N, grid::EE_POS_SUGGESTED_THREADS, grid::GRID_MAX_SOLVES_PER_BLOCK, grid::EE_POS_LDS_PER_SOLVE, grid::EE_POS_OUT_PER_SOLVE, &c))) return rc;
+        hipLaunchKernelGGL((grid::end_effector_pose_kernel<T>), c.grid, c.block, c.lds, (hipStream_t)stream, d_out, d_q, stride, rm, N);
+    } else if (which == 1) {
+        if ((rc = make_launch<T>(h, N, grid::DEE_POS_SUGGESTED_THREADS, grid::GRID_MAX_SOLVES_PER_BLOCK, grid::DEE_POS_LDS_PER_SOLVE, grid::DEE_POS_OUT_PER_SOLVE, &c))) return rc;
+        hipLaunchKernelGGL((grid::end_effector_pose_gradient_kernel<T>), c.grid, c.block, c.lds, (hipStream_t)stream, d_out, d_q, stride, rm, N);
+    } else {
+        if ((rc = make_launch<T>(h, N, grid::D2EE_POS_SUGGESTED_THREADS, grid::GRID_MAX_SOLVES_PER_BLOCK, grid::D2EE_POS_LDS_PER_SOLVE, grid::D2EE_POS_OUT_PER_SOLVE, &c))) return rc;
+        hipLaunchKernelGGL((grid::end_effector_pose_gradient_hessian_kernel<T>), c.grid, c.block, c.lds, (hipStream_t)stream, d_out, d_dee, d_q, stride, rm, N);
+    }
+    GRID_TRY(hipGetLastError());
+    return 0;
+}
+
+// grows one device staging buffer to at least `count` elements (the caller holds alloc_lock)
+template <typename T>
+static int ee_grow(T **buf, size_t *cap, size_t count) {
+    if (*cap >= count) return 0;
+    if (*buf) GRID_TRY(hipFree(*buf));
+    *buf = nullptr;
+    *cap = 0;
+    GRID_TRY(hipMalloc((void **)buf, count * sizeof(T)));
+    *cap = count;
+    return 0;
+}
+
+// Host buffers in, host buffers out, synchronous.  The handle's kinematics staging is allocated here on first use; the Hessian's holds at most
+// 1 GiB (like the second-order buffers) and longer batches pass through it in chunks.
+template <typename T>
+static int ee_host(grid_handle *h, const T *h_q, int stride, int N, T *h_out, T *h_dee, int which) {
+    int rc = host_prologue<T>(h, N);
+    if (rc || N == 0) return rc;
+    if (!h_q || !h_out) return fail_msg(hipErrorInvalidValue, "null input or output pointer");
+    if (stride < (int)grid::NUM_JOINTS) {
+        snprintf(g_err, sizeof(g_err), "stride %d is smaller than the %d joint positions of a solve", stride, (int)grid::NUM_JOINTS);
+        return (int)hipErrorInvalidValue;
+    }
+    GRID_ON_DEVICE(h);
+    if ((rc = ensure_typed<T>(h))) return rc;
+    const size_t rec = EE_REC[which], grad = EE_REC[1];
+    const bool dee = which == 2 && h_dee != nullptr;
+    size_t chunk = (size_t)N;
+    const size_t cap = ((size_t)1 << 30) / (rec * sizeof(T));
+    if (chunk > cap) chunk = cap > 0 ? cap : 1;
+    ee_stage<T> &st = ee_staging<T>(h);
+    {
+        std::lock_guard<std::mutex> lock(h->alloc_lock);
+        if ((rc = ee_grow<T>(&st.d_q, &st.q_cap, (size_t)stride * chunk))) return rc;
+        if ((rc = ee_grow<T>(&st.d_out, &st.out_cap, rec * chunk))) return rc;
+        if (dee && (rc = ee_grow<T>(&st.d_dee, &st.dee_cap, grad * chunk))) return rc;
+    }
+    hipStream_t s = h->streams[0];
+    for (size_t k0 = 0; k0 < (size_t)N; k0 += chunk) {
+        const size_t cnt = (k0 + chunk <= (size_t)N) ? chunk : (size_t)N - k0;
+        GRID_H2D(st.d_q, h_q + k0 * stride, (size_t)stride * cnt);
+        if ((rc = ee_device<T>(h, st.d_q, stride, (int)cnt, st.d_out, dee ? st.d_dee : nullptr, (void *)s, which))) return rc;
+        GRID_D2H(h_out + k0 * rec, st.d_out, rec * cnt);
+        if (dee) GRID_D2H(h_dee + k0 * grad, st.d_dee, grad * cnt);
+    }
+    GRID_TRY(hipStreamSynchronize(s));
+    return 0;
+}
+
+template <typename T>
+static void ee_release(ee_stage<T> &st) {
+    if (st.d_q) (void)hipFree(st.d_q);
+    if (st.d_out) (void)hipFree(st.d_out);
+    if (st.d_dee) (void)hipFree(st.d_dee);
+    st = ee_stage<T>();
+}
+
 // ---------------------------------------------------------------------------------------------------------------- multi-GPU driver
 // One process, G handles (one per GPU): the batch [0, N) is cut into G contiguous ranges of ceil(N/G) solves (SURVEY.md section 8(e),
 // 16 384 total -> 16 384/G per GPU, no collective).  Every device has its own robotModel copy and stream.
@@ -647,6 +746,8 @@ int grid_close(grid_handle *h) {
         }
         grid::close_grid<float>(h->streams, h->f32.d_robotModel, h->f32.hd_data);
         if (h->so_done) (void)hipEventDestroy(h->so_done);
+        ee_release(h->ee32);
+        ee_release(h->ee64);
     )
     delete h;
     return 0;
@@ -797,6 +898,50 @@ int grid_idsva_so_host_f64(grid_handle *h, const double *h_q_qd_u, const double 
 }
 int grid_fdsva_so_host_f64(grid_handle *h, const double *h_q_qd_u, int num_timesteps, double gravity, double *h_df2) {
     GRID_GUARDED(return so_host<double>(h, h_q_qd_u, nullptr, num_timesteps, gravity, h_df2, 1);)
+}
+
+// ---- end-effector kinematics
+int grid_num_end_effectors(void) { return grid::NUM_EES; }
+int grid_end_effector_joints(int *out) {
+    if (!out) return fail_msg(hipErrorInvalidValue, "grid_end_effector_joints: null result pointer");
+    for (int e = 0; e < grid::NUM_EES; e++) out[e] = grid::GRID_EE_JOINTS[e];
+    return 0;
+}
+int grid_end_effector_pose_device(grid_handle *h, const float *d_q, int stride_q, int num_timesteps, float *d_eePos, void *stream) {
+    GRID_GUARDED(return ee_device<float>(h, d_q, stride_q, num_timesteps, d_eePos, nullptr, stream, 0);)
+}
+int grid_end_effector_pose_gradient_device(grid_handle *h, const float *d_q, int stride_q, int num_timesteps, float *d_deePos, void *stream) {
+    GRID_GUARDED(return ee_device<float>(h, d_q, stride_q, num_timesteps, d_deePos, nullptr, stream, 1);)
+}
+int grid_end_effector_pose_gradient_hessian_device(grid_handle *h, const float *d_q, int stride_q, int num_timesteps, float *d_d2eePos, float *d_deePos, void *stream) {
+    GRID_GUARDED(return ee_device<float>(h, d_q, stride_q, num_timesteps, d_d2eePos, d_deePos, stream, 2);)
+}
+int grid_end_effector_pose_host(grid_handle *h, const float *h_q, int stride_q, int num_timesteps, float *h_eePos) {
+    GRID_GUARDED(return ee_host<float>(h, h_q, stride_q, num_timesteps, h_eePos, nullptr, 0);)
+}
+int grid_end_effector_pose_gradient_host(grid_handle *h, const float *h_q, int stride_q, int num_timesteps, float *h_deePos) {
+    GRID_GUARDED(return ee_host<float>(h, h_q, stride_q, num_timesteps, h_deePos, nullptr, 1);)
+}
+int grid_end_effector_pose_gradient_hessian_host(grid_handle *h, const float *h_q, int stride_q, int num_timesteps, float *h_d2eePos, float *h_deePos) {
+    GRID_GUARDED(return ee_host<float>(h, h_q, stride_q, num_timesteps, h_d2eePos, h_deePos, 2);)
+}
+int grid_end_effector_pose_device_f64(grid_handle *h, const double *d_q, int stride_q, int num_timesteps, double *d_eePos, void *stream) {
+    GRID_GUARDED(return ee_device<double>(h, d_q, stride_q, num_timesteps, d_eePos, nullptr, stream, 0);)
+}
+int grid_end_effector_pose_gradient_device_f64(grid_handle *h, const double *d_q, int stride_q, int num_timesteps, double *d_deePos, void *stream) {
+    GRID_GUARDED(return ee_device<double>(h, d_q, stride_q, num_timesteps, d_deePos, nullptr, stream, 1);)
+}
+int grid_end_effector_pose_gradient_hessian_device_f64(grid_handle *h, const double *d_q, int stride_q, int num_timesteps, double *d_d2eePos, double *d_deePos, void *stream) {
+    GRID_GUARDED(return ee_device<double>(h, d_q, stride_q, num_timesteps, d_d2eePos, d_deePos, stream, 2);)
+}
+int grid_end_effector_pose_host_f64(grid_handle *h, const double *h_q, int stride_q, int num_timesteps, double *h_eePos) {
+    GRID_GUARDED(return ee_host<double>(h, h_q, stride_q, num_timesteps, h_eePos, nullptr, 0);)
+}
+int grid_end_effector_pose_gradient_host_f64(grid_handle *h, const double *h_q, int stride_q, int num_timesteps, double *h_deePos) {
+    GRID_GUARDED(return ee_host<double>(h, h_q, stride_q, num_timesteps, h_deePos, nullptr, 1);)
+}
+int grid_end_effector_pose_gradient_hessian_host_f64(grid_handle *h, const double *h_q, int stride_q, int num_timesteps, double *h_d2eePos, double *h_deePos) {
+    GRID_GUARDED(return ee_host<double>(h, h_q, stride_q, num_timesteps, h_d2eePos, h_deePos, 2);)
 }
 
 int grid_forward_dynamics_gradient_single_timing(grid_handle *h, const float *h_q_qd_u, int reps, float gravity, float *h_df_du, double *us_per_call) {

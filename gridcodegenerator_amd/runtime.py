@@ -178,8 +178,11 @@ class GridLibrary:
 
     def host_f64(self, algorithm, *arrays, gravity=9.81):
         """T = double host-buffer entry points: algorithm in {inverse_dynamics, inverse_dynamics_gradient, direct_minv, forward_dynamics, aba,
-        idsva_so, fdsva_so}; arrays as for the float methods (q_qd[, qdd] / q / q_qd_u[, qdd]) in float64."""
+        idsva_so, fdsva_so, end_effector_pose, end_effector_pose_gradient, end_effector_pose_gradient_hessian}; arrays as for the float methods
+        (q_qd[, qdd] / q / q_qd_u[, qdd]) in float64."""
         n = self.n
+        if algorithm in ("end_effector_pose", "end_effector_pose_gradient", "end_effector_pose_gradient_hessian"):
+            return self._ee_host(("end_effector_pose", "end_effector_pose_gradient", "end_effector_pose_gradient_hessian").index(algorithm), arrays[0], np.float64)
         P = lambda a: ctypes.c_void_p(None) if a is None else ctypes.c_void_p(a.ctypes.data)
         # same column rules as the float methods; entry points without a stride argument read exactly 3n values per solve
         first = {"inverse_dynamics": (2 * n, 3 * n), "inverse_dynamics_gradient": (2 * n, 3 * n), "direct_minv": (n, 2 * n, 3 * n)}.get(algorithm, 3 * n)
@@ -272,6 +275,57 @@ class GridLibrary:
         us = ctypes.c_double()
         self._check(self.lib.grid_forward_dynamics_gradient_single_timing(self.handle, _ptr(x), ctypes.c_int(reps), ctypes.c_float(gravity), _ptr(out), ctypes.byref(us)))
         return out, us.value
+
+    # ---- end-effector kinematics (every leaf joint is an end effector): pose (N, 6E), gradient (N, 6En), Hessian (N, 6En^2); q of width n or 3n
+    @property
+    def num_end_effectors(self):
+        return self.lib.grid_num_end_effectors()
+
+    @property
+    def end_effector_joints(self):
+        E = self.num_end_effectors
+        out = (ctypes.c_int * E)()
+        self._check(self.lib.grid_end_effector_joints(out))
+        return list(out)
+
+    def _ee_cols(self):
+        n, E = self.n, self.num_end_effectors
+        return 6 * E, 6 * E * n, 6 * E * n * n
+
+    def _ee_host(self, which, q, dtype):
+        x = self._host_in(q, (self.n, 3 * self.n), "q", dtype)
+        N = x.shape[0]
+        P = lambda a: ctypes.c_void_p(None) if a is None else ctypes.c_void_p(a.ctypes.data)
+        sfx = "_f64" if dtype == np.float64 else ""
+        out = np.empty((N, self._ee_cols()[which]), dtype=dtype)
+        if which == 2:
+            dee = np.empty((N, self._ee_cols()[1]), dtype=dtype)
+            self._check(self.lib["grid_end_effector_pose_gradient_hessian_host" + sfx](self.handle, P(x), ctypes.c_int(x.shape[1]), ctypes.c_int(N), P(out), P(dee)))
+            return out, dee
+        fn = self.lib[("grid_end_effector_pose_host", "grid_end_effector_pose_gradient_host")[which] + sfx]
+        self._check(fn(self.handle, P(x), ctypes.c_int(x.shape[1]), ctypes.c_int(N), P(out)))
+        return out
+
+    def end_effector_pose_host(self, q):
+        return self._ee_host(0, q, np.float32)
+
+    def end_effector_pose_gradient_host(self, q):
+        return self._ee_host(1, q, np.float32)
+
+    def end_effector_pose_gradient_hessian_host(self, q):
+        """returns (d2eePos (N, 6En^2), deePos (N, 6En))"""
+        return self._ee_host(2, q, np.float32)
+
+    def end_effector_pose_device(self, d_q, N, d_eePos, stride=None, stream=0):
+        self._check(self.lib.grid_end_effector_pose_device(self.handle, _ptr(d_q), ctypes.c_int(stride or self.n), ctypes.c_int(N), _ptr(d_eePos), ctypes.c_void_p(stream)))
+
+    def end_effector_pose_gradient_device(self, d_q, N, d_deePos, stride=None, stream=0):
+        self._check(self.lib.grid_end_effector_pose_gradient_device(self.handle, _ptr(d_q), ctypes.c_int(stride or self.n), ctypes.c_int(N), _ptr(d_deePos),
+                                                                    ctypes.c_void_p(stream)))
+
+    def end_effector_pose_gradient_hessian_device(self, d_q, N, d_d2eePos, d_deePos=None, stride=None, stream=0):
+        self._check(self.lib.grid_end_effector_pose_gradient_hessian_device(self.handle, _ptr(d_q), ctypes.c_int(stride or self.n), ctypes.c_int(N), _ptr(d_d2eePos),
+                                                                            _ptr(d_deePos), ctypes.c_void_p(stream)))
 
     # ---- device-pointer entry points (asynchronous on `stream`)
     def forward_dynamics_gradient_device(self, d_q_qd_u, N, d_df_du, stride=None, gravity=9.81, stream=0):

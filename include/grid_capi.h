@@ -145,6 +145,33 @@ int grid_aba_host_f64(grid_handle *h, const double *h_q_qd_tau, int num_timestep
 int grid_idsva_so_host_f64(grid_handle *h, const double *h_q_qd_u, const double *h_qdd, int num_timesteps, double gravity, double *h_idsva_so);
 int grid_fdsva_so_host_f64(grid_handle *h, const double *h_q_qd_u, int num_timesteps, double gravity, double *h_df2);
 
+/* End-effector kinematics (reference algorithms/_eepose_gradient_hessian.py, emitted by the reference's gen_all_code for every fixed-base robot).
+ * Every leaf joint is an end effector (ascending id); the pose of one is [x, y, z, roll, pitch, yaw] of its link frame in the base frame (no tool offset).
+ * Layouts (k = batch index):  eePos [k*6E + 6e + c],  deePos [k*6En + 6(e*n + j) + c],  d2eePos [k*6En^2 + e*6n^2 + c*n^2 + i*n + j]
+ * (the reference's Hessian layout for E = 1; for E > 1 every end effector has its own 6n^2 block - the reference's offsets overlap them).
+ * q is read with a caller stride >= n (n: the reference's USE_COMPRESSED_MEM, 3n: q_qd_u).  No gravity argument (kinematics). */
+int grid_num_end_effectors(void);
+int grid_end_effector_joints(int *out); /* writes the grid_num_end_effectors() leaf joint ids */
+/* replace end_effector_pose_kernel<T> / end_effector_pose_gradient_kernel<T> / end_effector_pose_gradient_hessian_kernel<T>
+ * (reference algorithms/_eepose_gradient_hessian.py: gen_end_effector_pose_kernel, _gradient_kernel, _gradient_hessian_kernel): device buffers, asynchronous
+ * on `stream`, nothing allocated.  d_deePos of the Hessian entry point may be NULL (otherwise it receives the gradient, as the reference's kernel writes both) */
+int grid_end_effector_pose_device(grid_handle *h, const float *d_q, int stride_q, int num_timesteps, float *d_eePos, void *stream);
+int grid_end_effector_pose_gradient_device(grid_handle *h, const float *d_q, int stride_q, int num_timesteps, float *d_deePos, void *stream);
+int grid_end_effector_pose_gradient_hessian_device(grid_handle *h, const float *d_q, int stride_q, int num_timesteps, float *d_d2eePos, float *d_deePos, void *stream);
+/* replace the host wrappers end_effector_pose<T,USE_COMPRESSED_MEM> / end_effector_pose_gradient<T,...> / end_effector_pose_gradient_hessian<T,...>
+ * (reference algorithms/_eepose_gradient_hessian.py: gen_end_effector_pose_host and its twins): host buffers, synchronous, num_timesteps <= max_timesteps.
+ * Their device staging is allocated by the first kinematics call on a handle; the Hessian's is at most 1 GiB and longer batches pass through it in chunks.
+ * h_deePos of the Hessian entry point may be NULL. */
+int grid_end_effector_pose_host(grid_handle *h, const float *h_q, int stride_q, int num_timesteps, float *h_eePos);
+int grid_end_effector_pose_gradient_host(grid_handle *h, const float *h_q, int stride_q, int num_timesteps, float *h_deePos);
+int grid_end_effector_pose_gradient_hessian_host(grid_handle *h, const float *h_q, int stride_q, int num_timesteps, float *h_d2eePos, float *h_deePos);
+int grid_end_effector_pose_device_f64(grid_handle *h, const double *d_q, int stride_q, int num_timesteps, double *d_eePos, void *stream);
+int grid_end_effector_pose_gradient_device_f64(grid_handle *h, const double *d_q, int stride_q, int num_timesteps, double *d_deePos, void *stream);
+int grid_end_effector_pose_gradient_hessian_device_f64(grid_handle *h, const double *d_q, int stride_q, int num_timesteps, double *d_d2eePos, double *d_deePos, void *stream);
+int grid_end_effector_pose_host_f64(grid_handle *h, const double *h_q, int stride_q, int num_timesteps, double *h_eePos);
+int grid_end_effector_pose_gradient_host_f64(grid_handle *h, const double *h_q, int stride_q, int num_timesteps, double *h_deePos);
+int grid_end_effector_pose_gradient_hessian_host_f64(grid_handle *h, const double *h_q, int stride_q, int num_timesteps, double *h_d2eePos, double *h_deePos);
+
 /* in-kernel timing probe: replaces forward_dynamics_gradient_single_timing<T> (reference :236-248); returns microseconds per solve */
 int grid_forward_dynamics_gradient_single_timing(grid_handle *h, const float *h_q_qd_u, int reps, float gravity, float *h_df_du, double *us_per_call);
 
