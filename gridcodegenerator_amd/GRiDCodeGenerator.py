@@ -139,7 +139,7 @@ class GRiDCodeGenerator:
         gen_forward_dynamics_gradient_host, gen_forward_dynamics_gradient, gen_forward_dynamics_gradient_device_function_call, \
         gen_tip_frame_link_constants, gen_tip_frame_joint_offset, gen_tip_frame_library, gen_forward_dynamics_gradient_inner_tip, \
         gen_forward_dynamics_gradient_inner_tip_function_call, gen_tip_frame_gradient, gen_tip_frame_fused_so, \
-        gen_inverse_dynamics_inner_tip, gen_inverse_dynamics_gradient_inner_tip, gen_forward_dynamics_inner_tip, gen_direct_minv_inner_tip, gen_tip_frame_components, \
+        gen_inverse_dynamics_inner_tip, gen_inverse_dynamics_gradient_inner_tip, gen_forward_dynamics_inner_tip, gen_direct_minv_inner_tip, gen_crba_inner_tip, gen_tip_frame_components, \
         gen_branch_frame_plan, gen_branch_frame_constants, gen_branch_frame_library, gen_branch_frame_components, gen_forward_dynamics_gradient_inner_branch, gen_forward_dynamics_gradient_inner_branch_stream, \
         gen_forward_dynamics_gradient_inner_branch_function_call
 
@@ -151,9 +151,14 @@ class GRiDCodeGenerator:
         gen_end_effector_pose_gradient_hessian_inner, gen_end_effector_pose_gradient_hessian_device, gen_end_effector_pose_gradient_hessian_kernel, \
         gen_end_effector_pose_gradient_hessian_host, gen_eepose_and_derivatives
 
+    # joint-space inertia matrix (reference algorithms/_crba.py)
+    from .algorithms import gen_crba_inner_temp_mem_size, gen_crba_inner_function_call, gen_crba_inner, gen_crba_device_temp_mem_size, gen_crba_device, \
+        gen_crba_kernel, gen_crba_host, gen_crba_constants, gen_crba
+
     # NumPy debug helpers with the reference's names and signatures (reference GRiDCodeGenerator.py:50-51, README "Additional Features")
     from ._test import test_rnea, test_minv, test_rnea_grad, test_fd_grad
     from ._test import test_end_effector_pose, test_end_effector_pose_gradient, test_end_effector_pose_hessian
+    from ._test import test_crba
 
     def __init__(self, robotObj, DEBUG_MODE=False, NEED_PRINT_MAT=False, USE_DYNAMIC_SHARED_MEM=True, FILE_NAMESPACE="grid", COLS_PER_LANE=None, tuning=None):
         if not USE_DYNAMIC_SHARED_MEM:
@@ -455,6 +460,7 @@ class GRiDCodeGenerator:
                                  "gpuErrchk(hipHostFree(hd_data->h_dc_du)); gpuErrchk(hipHostFree(hd_data->h_df_du));",
                                  "// kinematics buffers: allocated by the first end_effector_pose* host call (grid_ee_reserve)",
                                  "grid_ee_release(&hd_data->d_eePos, &hd_data->h_eePos); grid_ee_release(&hd_data->d_deePos, &hd_data->h_deePos); grid_ee_release(&hd_data->d_d2eePos, &hd_data->h_d2eePos);",
+                                 "grid_ee_release(&hd_data->d_M, &hd_data->h_M); // (allocated by the first crba host call)",
                                  "free(hd_data);",
                                  "for(int i=0; i<" + str(MAX_STREAMS) + "; i++){gpuErrchk(hipStreamDestroy(streams[i]));} free(streams);"])
         self.gen_add_end_function()
@@ -528,6 +534,7 @@ class GRiDCodeGenerator:
         self.gen_fdsva_so(use_thread_group)
         if not self.nested:
             self.gen_eepose_and_derivatives(use_thread_group)  # (outer namespace only: the nested `wide` instance carries the second-order kernels alone)
+            self.gen_crba(use_thread_group)  # (outer namespace only, after the kinematics: its host wrappers reserve d_M / h_M with grid_ee_reserve)
         if not self.nested:
             self.gen_init_close_grid()
 
@@ -589,6 +596,11 @@ class GRiDCodeGenerator:
                       "    __device__ end_effector_pose_gradient_hessian_device<T>(T *d2, T *s_deePos, const T *s_q, T *s_work, const robotModel<T> *d_robotModel, const int lane, const bool active)",
                       "    __global__ end_effector_pose_gradient_hessian_kernel<T>(T *d_d2eePos, T *d_deePos, const T *d_q, const int stride_q, const robotModel<T> *d_robotModel, const int NUM_TIMESTEPS)",
                       "    __host__   end_effector_pose_gradient_hessian<T,USE_COMPRESSED_MEM=false>(gridData<T> *hd_data, const robotModel<T> *d_robotModel, const int num_timesteps, const dim3 block_dimms, const dim3 thread_dimms, hipStream_t *streams)",
+                      "",
+                      "    joint-space inertia matrix (dense symmetric M[k*n*n + col*n + row]; gravity is accepted and unused; the host wrappers allocate d_M / h_M on first use):",
+                      "    __device__ crba_device<T>(T *s_M, const T *s_q, T *s_work, const robotModel<T> *d_robotModel, const int lane[, const int off_sp])",
+                      "    __global__ crba_kernel<T>(T *d_M, const T *d_q_qd, const int stride_q_qd, const robotModel<T> *d_robotModel, const T gravity, const int NUM_TIMESTEPS)",
+                      "    __host__   crba<T,USE_COMPRESSED_MEM=false>(gridData<T> *hd_data, const robotModel<T> *d_robotModel, const T gravity, const int num_timesteps, const dim3 block_dimms, const dim3 thread_dimms, hipStream_t *streams)",
                       "",
                       "Every host function also exists as NAME_single_timing and NAME_compute_only (no streams argument).",
                       "",

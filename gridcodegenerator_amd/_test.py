@@ -271,3 +271,26 @@ def test_end_effector_pose_gradient(self, q):
 def test_end_effector_pose_hessian(self, q):
     """(E, 6, n, n): d2 pose / d q_i d q_j (symmetric; 0 unless both joints are on the leaf's root path)"""
     return _ee_all(self, q, 2)[2]
+
+
+def test_crba(self, q):
+    """(n, n): the joint-space inertia matrix M(q) by the composite rigid body algorithm (dense, symmetric; 0 where neither joint is an
+    ancestor of the other).  Composites fold into parents leaves first; F = I^C_j S_j walks up the root path of j."""
+    m = self.model
+    n = m.n
+    X = _Xs(self, q)
+    IC = [m.I[j].copy() for j in range(n)]
+    M = np.zeros((n, n))
+    for j in range(n - 1, -1, -1):  # (ids are parent-first: every child is folded in before its parent is reached)
+        p = m.parent[j]
+        if p != -1:
+            IC[p] += X[j].T @ IC[j] @ X[j]
+    for j in range(n):
+        F = IC[j][:, m.S_index[j]].copy()
+        M[j, j] = F[m.S_index[j]]
+        i = j
+        while m.parent[i] != -1:
+            F = X[i].T @ F
+            i = m.parent[i]
+            M[i, j] = M[j, i] = F[m.S_index[i]]
+    return M

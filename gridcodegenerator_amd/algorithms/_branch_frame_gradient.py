@@ -629,6 +629,8 @@ _BRANCH_MODES = {
            "T *s_qdd, const T *s_qd, const T *s_u, T *s_X, T *s_SP, const robotModel<T> *d_robotModel, const T gravity, const int lane"),
     "minv": ("direct_minv_inner_branch", "Compute the inverse of the mass matrix (dense, symmetric) into LDS",
              "T *s_Minv, T *s_X, T *s_SP, const robotModel<T> *d_robotModel, const int lane"),
+    "crba": ("crba_inner_branch", "Compute the joint-space inertia matrix M(q) (dense, symmetric) into LDS",
+             "T *s_M, T *s_X, T *s_SP, const robotModel<T> *d_robotModel, const int lane"),
 }
 
 
@@ -643,8 +645,8 @@ def _emit_branch_inner(self, mode, use_thread_group=False):
     if stream:
         mode = "fdgrad"
     grad = mode in ("fdgrad", "idgrad")      # needs the Coriolis composites and the derivative entries
-    kin = mode != "minv"                      # needs velocities / accelerations
-    needs_M = mode in ("fdgrad", "fd", "minv")
+    kin = mode not in ("minv", "crba")        # needs velocities / accelerations
+    needs_M = mode in ("fdgrad", "fd", "minv", "crba")
     qdd_in = mode in ("id", "idgrad")        # joint accelerations are an input (id: the pointer may be null = zero)
     m = self.model
     n = m.n
@@ -660,7 +662,8 @@ def _emit_branch_inner(self, mode, use_thread_group=False):
               "id": "s_c receives the joint torques (lane of joint j writes s_c[j]); s_qddin may be nullptr (zero accelerations)",
               "idgrad": "s_dc_du receives dc/du in the device layout [col*n + row], col in [0,2n) = [d/dq | d/dqd]",
               "fd": "s_qdd receives the joint accelerations (it also holds tau - c on the way)",
-              "minv": "s_Minv receives the dense symmetric inverse of the joint-space inertia (leading dimension GRID_MINV_LD; zero between base-rooted components)"}[mode]
+              "minv": "s_Minv receives the dense symmetric inverse of the joint-space inertia (leading dimension GRID_MINV_LD; zero between base-rooted components)",
+              "crba": "s_M receives the dense joint-space inertia (leading dimension GRID_MINV_LD): every pair once, so exactly symmetric; exact zeros between base-rooted components and between joints of which neither is an ancestor of the other"}[mode]
     self.gen_add_func_doc(fdoc + ", every branch of the tree in the frame of its tip link",
                           ["robots whose joints are all revolute (see the module notes of algorithms/_branch_frame_gradient.py)", outdoc,
                            "the caller must grid_wave_sync() before other lanes read the result"],
@@ -1176,7 +1179,7 @@ def _emit_branch_inner(self, mode, use_thread_group=False):
             A("*((act%d && own != %d) ? &s_df_du[(%d + pj%d)*%d + jid] : s_trash) = lo_d;" % (i, i, yo, i, n))
             walk_close()
         self.gen_add_end_control_flow()
-    else:  # fd, minv: only the joint-space inertia, M[i][k] = S_i . (I^C_k S_k) for the ancestors-or-self i of this lane's joint k
+    else:  # fd, minv, crba: only the joint-space inertia, M[i][k] = S_i . (I^C_k S_k) for the ancestors-or-self i of this lane's joint k
         A("T t1[6]; grid_rbi_mul(t1, IC, S);")
         if bfam:
             for ln in _t1m_lines():
@@ -1209,6 +1212,25 @@ def _emit_branch_inner(self, mode, use_thread_group=False):
     shapes = P["shapes"]
     NCmax = max(len(s_) for s_ in shapes)
     ancs = [_anc_local(s_) for s_ in shapes]
+    if mode == "crba":  # the minv mode stopped before the factorisation: scatter the tree-sparse M into the dense record
+        A("// dense M: zeros first, then the lane of joint k writes M[i][k] of its ancestors-or-self i into both slots (i, k) and (k, i)")
+        A("for (int e = lane; e < %d; e += GRID_LANES_PER_SOLVE) { s_M[e] = Z; }" % (n * ld))
+        self.gen_add_sync(use_thread_group)
+        A("if (active) {", True)
+        for si, sig in enumerate(shapes):
+            an = ancs[si]
+            midx = {}
+            for k in range(len(sig)):
+                for i in an[k] + [k]:
+                    midx[(i, k)] = len(midx)
+            A("%sif (shape == %d) {" % ("" if si == 0 else "else ", si), True)
+            for k in range(len(sig)):
+                A("if (li == %d) { %s }" % (k, " ".join("{ const T v = s_Mc[ubase + %d]; s_M[%d*(cbase + %d) + jid] = v; s_M[%d*jid + cbase + %d] = v; }" % (midx[(i, k)], ld, i, ld, i)
+                                                      for i in an[k] + [k])))
+            self.gen_add_end_control_flow()
+        self.gen_add_end_control_flow()
+        self.gen_add_end_function()
+        return
     with_rhs = mode in ("fdgrad", "fd")
     park = mode in ("fdgrad", "minv")
     R32 = (lambda e: "static_cast<T>(static_cast<float>(%s))" % e) if "factor" in tuple(self.tuning.get("round_probe", ())) else (lambda e: e)

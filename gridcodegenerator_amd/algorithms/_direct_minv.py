@@ -54,6 +54,22 @@ def gen_direct_minv_inner_header(self):
     self.gen_add_code_line("void direct_minv_inner(T *s_Minv, const T *s_X, T *s_U, T *s_T, const robotModel<T> *d_robotModel, const int lane) {", True)
 
 
+def gen_inertia_to_parent(self, i, dst, use_thread_group=False):
+    """Second half of the two-sided update dst += X_i^T A X_i of a symmetric 6x6 A held one column per lane (column cI on the lanes with isIA):
+    the caller has formed Tc = X_i^T A[:, cI]; it goes through LDS as a 6x6 transpose (s_T, double buffered by the depth parity of joint i),
+    and the second one-sided product adds X_i^T (X_i^T A)[cI, :]^T to column cI of dst (valid because A is symmetric).  Used by the backward
+    sweeps of direct_minv (articulated inertias) and crba (composite inertias); needs X, Tc, Tr, cI, isIA and s_T in scope."""
+    tbuf = (self.model.depth[i] & 1) * 40
+    self.gen_add_code_line("if (isIA) {", True)
+    self.gen_add_code_line("#pragma unroll")
+    self.gen_add_code_line("for (int r = 0; r < 6; r++) { s_T[%d + 6*r + cI] = Tc[r]; }" % tbuf)
+    self.gen_add_end_control_flow()
+    self.gen_add_sync(use_thread_group)
+    self.gen_add_code_line("#pragma unroll")
+    self.gen_add_code_line("for (int r = 0; r < 6; r++) { Tr[r] = s_T[%d + 6*cI + r]; }" % tbuf)
+    self.gen_add_code_line("grid_xtmul_peq(%s, X, Tr); grid_pin6(%s);" % (dst, dst))
+
+
 def gen_direct_minv_inner_body(self, use_thread_group=False, bwd_hook=None, fwd_hook=None):
     m = self.model
     n = m.n
@@ -83,7 +99,6 @@ def gen_direct_minv_inner_body(self, use_thread_group=False, bwd_hook=None, fwd_
 
     def post_b(i):
         s, p = m.S_index[i], m.parent[i]
-        tbuf = (m.depth[i] & 1) * 40  # the transpose scratch is double buffered by depth parity
         self.gen_add_code_line("{", True)
         self.gen_add_code_line("// U = IA[:, S] lives in the lane that owns that column: broadcast it inside the lane group (no LDS hand-off, no sync)")
         self.gen_add_code_line("T U[6];")
@@ -127,14 +142,7 @@ def gen_direct_minv_inner_body(self, use_thread_group=False, bwd_hook=None, fwd_
                 self.gen_add_code_line("#pragma unroll")
                 self.gen_add_code_line("for (int r = 0; r < 6; r++) { F_%d[r] += isIA ? static_cast<T>(0) : Tc[r]; }" % p)
                 self.gen_add_code_line("grid_pin6(F_%d);" % p)
-            self.gen_add_code_line("if (isIA) {", True)
-            self.gen_add_code_line("#pragma unroll")
-            self.gen_add_code_line("for (int r = 0; r < 6; r++) { s_T[%d + 6*r + cI] = Tc[r]; }" % tbuf)
-            self.gen_add_end_control_flow()
-            self.gen_add_sync(use_thread_group)
-            self.gen_add_code_line("#pragma unroll")
-            self.gen_add_code_line("for (int r = 0; r < 6; r++) { Tr[r] = s_T[%d + 6*cI + r]; }" % tbuf)
-            self.gen_add_code_line("grid_xtmul_peq(IA_%d, X, Tr); grid_pin6(IA_%d);" % (p, p))
+            gen_inertia_to_parent(self, i, "IA_%d" % p, use_thread_group)
         self.gen_add_end_control_flow()
 
     self.gen_tree_traversal(pre_b, post_b)

@@ -831,12 +831,12 @@ def _emit_force_only(self, with_qdd):
     self.gen_add_code_line("grid_suffix_sum(fC, mkd); // force transmitted across joint j: sum over the links j..n-1")
 
 
-def _emit_mass_matrix_factor(self, use_thread_group, rhs_expr=None):
-    """IC -> t1 = I^C S, record [S | rhs | . | S lin about pB], M column by dots, hand-off, wave-uniform factorisation (leaves Uf*, rd*; rhs[] if asked)."""
+def _emit_mass_matrix_assembly(self, use_thread_group, rhs_expr=None, sink=None):
+    """IC -> t1 = I^C S, record [S | rhs | . | S lin about pB], M column by dots: leaves Mcol[k] = M[base + k][lane] in registers, valid for the rows
+    k <= pos of the lane's own chain (rhs[] if asked).  sink(value expression) instead: emit the use of each entry inside the loop over k (no Mcol array)."""
     n = self.model.n
     L = self.tip_L
     Lp = (L + 3) // 4 * 4
-    ld = self.minv_ld
     bf = self.tip_jB is not None
     self.gen_add_code_line("T t1[6]; grid_rbi_mul(t1, IC, S);")
     if bf:
@@ -851,9 +851,10 @@ def _emit_mass_matrix_factor(self, use_thread_group, rhs_expr=None):
         self.gen_add_code_line("rec[8] = SB[0]; rec[9] = SB[1]; rec[10] = SB[2]; // linear part of S about pB")
     self.gen_add_end_control_flow()
     self.gen_add_sync(use_thread_group)
-    self.gen_add_code_line("T Mcol[%d]%s;" % (Lp, (", rhs[%d]" % L) if rhs_expr is not None else ""))
-    for k in range(L, Lp):
-        self.gen_add_code_line("Mcol[%d] = static_cast<T>(0);" % k)
+    if sink is None:
+        self.gen_add_code_line("T Mcol[%d]%s;" % (Lp, (", rhs[%d]" % L) if rhs_expr is not None else ""))
+        for k in range(L, Lp):
+            self.gen_add_code_line("Mcol[%d] = static_cast<T>(0);" % k)
     self.gen_add_code_line("#pragma unroll")
     self.gen_add_code_line("for (int k = 0; k < %d; k++) { // M[k][lane] = S_k . (I^C_lane S_lane), rows k <= lane of the lane's own chain" % L, True)
     nr = 12 if bf else 8
@@ -862,12 +863,25 @@ def _emit_mass_matrix_factor(self, use_thread_group, rhs_expr=None):
     self.gen_add_code_line("for (int r = 0; r < %d; r++) { g[r] = s_G[16*(base + k) + r]; }" % nr)
     if bf:
         self.gen_add_code_line("const T l0 = fam ? g[8] : g[3], l1 = fam ? g[9] : g[4], l2 = fam ? g[10] : g[5]; // linear part of S_k about this column's reference point")
-        self.gen_add_code_line("Mcol[k] = g[0]*t1m[0] + g[1]*t1m[1] + g[2]*t1m[2] + l0*t1m[3] + l1*t1m[4] + l2*t1m[5];")
+        val = "g[0]*t1m[0] + g[1]*t1m[1] + g[2]*t1m[2] + l0*t1m[3] + l1*t1m[4] + l2*t1m[5]"
     else:
-        self.gen_add_code_line("Mcol[k] = g[0]*t1[0] + g[1]*t1[1] + g[2]*t1[2] + g[3]*t1[3] + g[4]*t1[4] + g[5]*t1[5];")
+        val = "g[0]*t1[0] + g[1]*t1[1] + g[2]*t1[2] + g[3]*t1[3] + g[4]*t1[4] + g[5]*t1[5]"
+    if sink is None:
+        self.gen_add_code_line("Mcol[k] = %s;" % val)
+    else:
+        sink(val)
     if rhs_expr is not None:
         self.gen_add_code_line("rhs[k] = g[6];")
     self.gen_add_end_control_flow()
+
+
+def _emit_mass_matrix_factor(self, use_thread_group, rhs_expr=None):
+    """_emit_mass_matrix_assembly, hand-off of M through s_M, wave-uniform factorisation (leaves Uf*, rd*; rhs[] if asked)."""
+    n = self.model.n
+    L = self.tip_L
+    Lp = (L + 3) // 4 * 4
+    ld = self.minv_ld
+    _emit_mass_matrix_assembly(self, use_thread_group, rhs_expr)
     self.gen_add_code_line("if (lane < %d) {" % n, True)
     self.gen_add_code_line("#pragma unroll")
     self.gen_add_code_line("for (int k = 0; k < %d; k++) { s_M[%d*lane + k] = Mcol[k]; }" % (Lp, ld))
@@ -968,6 +982,32 @@ def gen_direct_minv_inner_tip(self, use_thread_group=False):
     self.gen_add_code_line("if (lane < %d) {" % n, True)
     _own_rows(self, "s_Minv[" + str(ld) + "*lane + %d]", "x[%d]")
     self.gen_add_end_control_flow()
+    self.gen_add_code_line("(void)gvec; (void)mku;")
+    self.gen_add_end_function()
+
+
+def gen_crba_inner_tip(self, use_thread_group=False):
+    """M (dense, symmetric): the assembly of direct_minv_inner_tip (same composites, same base-origin family) stopped before the factorisation."""
+    n = self.model.n
+    ld = self.minv_ld
+    L = self.tip_L
+    _tip_inner_header(self, "crba_inner_tip", "Compute the joint-space inertia matrix M(q) (dense, symmetric) into LDS",
+                      ["lane j owns column j: it writes M[i][j] for the rows i <= j of its own chain into both slots (i, j) and (j, i), so M is exactly symmetric;"
+                       + (" entries between different chains are exact zeros;" if self.tip_nseg > 1 else ""),
+                       "the caller must grid_wave_sync() before other lanes' entries are read"],
+                      ["s_M is the n x n output in LDS (leading dimension GRID_MINV_LD)",
+                       "s_X is this solve's compact X(q) storage", "s_G is LDS scratch for the per-joint hand-off records (16 values per joint)"],
+                      "T *s_M, const T *s_X, T *s_G", with_gravity=False, base_family=True)
+    _emit_link_setup(self, kinematics=False, base_family=True)
+    self.gen_add_code_line("T IC[10];")
+    self.gen_add_code_line("#pragma unroll")
+    self.gen_add_code_line("for (int r = 0; r < 10; r++) { IC[r] = I[r]; }")
+    self.gen_add_code_line("grid_suffix_sum(IC, mkd);")
+    if self.tip_nseg > 1:
+        self.gen_add_code_line("if (lane < %d) { for (int c = 0; c < %d; c++) { if (c < base || c >= base + %d) { s_M[%d*lane + c] = static_cast<T>(0); } } } // (other chains: this lane's row; its column is the other lanes' rows)" % (n, n, L, ld))
+    # every entry leaves as soon as it is formed (no array of M entries held across the loop: fewer live registers)
+    _emit_mass_matrix_assembly(self, use_thread_group, sink=lambda v: self.gen_add_code_line(
+        "if (lane < %d && k <= pos) { const T mk = %s; s_M[%d*(base + k) + lane] = mk; s_M[%d*lane + base + k] = mk; }" % (n, v, ld, ld)))
     self.gen_add_code_line("(void)gvec; (void)mku;")
     self.gen_add_end_function()
 

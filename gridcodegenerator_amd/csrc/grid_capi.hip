@@ -32,6 +32,7 @@ template <typename T>
 struct grid_typed {
     grid::robotModel<T> *d_robotModel = nullptr;
     grid::gridData<T> *hd_data = nullptr;
+    size_t M_cap = 0;  // elements of hd_data->d_M, the output staging of the crba host entry point (allocated by its first call; no pinned twin)
 };
 
 // staging of the kinematics host entry points (grid_end_effector_pose*_host): allocated by the first kinematics call on a handle, never by grid_init,
@@ -656,6 +657,47 @@ static void ee_release(ee_stage<T> &st) {
     st = ee_stage<T>();
 }
 
+// ---------------------------------------------------------------------------------------------------------------- joint-space inertia matrix
+template <typename T>
+static int crba_device(grid_handle *h, const T *d_q, int stride, int N, T *d_M, void *stream) {
+    int rc = check_args(h, N);
+    if (rc) return rc;
+    if ((rc = check_io(d_q, stride, (int)grid::NUM_JOINTS, d_M, N))) return rc;
+    if (N == 0) return 0;
+    GRID_ON_DEVICE(h);
+    if ((rc = ensure_typed<T>(h))) return rc;
+    launch_cfg c;
+    if ((rc = make_launch<T>(h, N, grid::CRBA_SUGGESTED_THREADS, grid::GRID_MAX_SOLVES_PER_BLOCK, grid::CRBA_LDS_PER_SOLVE, grid::CRBA_OUT_PER_SOLVE, &c))) return rc;
+    hipLaunchKernelGGL((grid::crba_kernel<T>), c.grid, c.block, c.lds, (hipStream_t)stream, d_M, d_q, stride, typed<T>(h).d_robotModel, (T)0, N);
+    GRID_TRY(hipGetLastError());
+    return 0;
+}
+
+// Host buffers in, host buffers out, synchronous.  The output is staged in the handle's own hd_data->d_M (null after init_gridData, allocated here on
+// first use and grown by longer calls, freed by close_grid) - no other entry point's buffer is borrowed, and no pinned h_M is allocated (the result
+// goes straight to the caller's buffer).
+template <typename T>
+static int crba_host(grid_handle *h, const T *h_q, int stride, int N, T *h_M) {
+    int rc = host_prologue<T>(h, N);
+    if (rc || N == 0) return rc;
+    if (!h_q || !h_M) return fail_msg(hipErrorInvalidValue, "null input or output pointer");
+    const size_t n = grid::NUM_JOINTS;
+    if (stride < (int)n || stride > 3 * (int)n) return fail_msg(hipErrorInvalidValue, "stride must be in [n, 3n] for host buffers (USE_COMPRESSED_MEM: 2n)");
+    GRID_ON_DEVICE(h);
+    if ((rc = ensure_typed<T>(h))) return rc;
+    grid::gridData<T> *d = typed<T>(h).hd_data;
+    {
+        std::lock_guard<std::mutex> lock(h->alloc_lock);
+        if ((rc = ee_grow<T>(&d->d_M, &typed<T>(h).M_cap, n * n * (size_t)N))) return rc;
+    }
+    hipStream_t s = h->streams[0];
+    GRID_H2D(d->d_q_qd_u, h_q, (size_t)stride * N);
+    if ((rc = crba_device<T>(h, d->d_q_qd_u, stride, N, d->d_M, (void *)s))) return rc;
+    GRID_D2H(h_M, d->d_M, n * n * N);
+    GRID_TRY(hipStreamSynchronize(s));
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- multi-GPU driver
 // One process, G handles (one per GPU): the batch [0, N) is cut into G contiguous ranges of ceil(N/G) solves (SURVEY.md section 8(e),
 // 16 384 total -> 16 384/G per GPU, no collective).  Every device has its own robotModel copy and stream.
@@ -942,6 +984,19 @@ int grid_end_effector_pose_gradient_host_f64(grid_handle *h, const double *h_q, 
 }
 int grid_end_effector_pose_gradient_hessian_host_f64(grid_handle *h, const double *h_q, int stride_q, int num_timesteps, double *h_d2eePos, double *h_deePos) {
     GRID_GUARDED(return ee_host<double>(h, h_q, stride_q, num_timesteps, h_d2eePos, h_deePos, 2);)
+}
+
+int grid_crba_device(grid_handle *h, const float *d_q, int stride_q, int num_timesteps, float *d_M, void *stream) {
+    GRID_GUARDED(return crba_device<float>(h, d_q, stride_q, num_timesteps, d_M, stream);)
+}
+int grid_crba_host(grid_handle *h, const float *h_q, int stride_q, int num_timesteps, float *h_M) {
+    GRID_GUARDED(return crba_host<float>(h, h_q, stride_q, num_timesteps, h_M);)
+}
+int grid_crba_device_f64(grid_handle *h, const double *d_q, int stride_q, int num_timesteps, double *d_M, void *stream) {
+    GRID_GUARDED(return crba_device<double>(h, d_q, stride_q, num_timesteps, d_M, stream);)
+}
+int grid_crba_host_f64(grid_handle *h, const double *h_q, int stride_q, int num_timesteps, double *h_M) {
+    GRID_GUARDED(return crba_host<double>(h, h_q, stride_q, num_timesteps, h_M);)
 }
 
 int grid_forward_dynamics_gradient_single_timing(grid_handle *h, const float *h_q_qd_u, int reps, float gravity, float *h_df_du, double *us_per_call) {

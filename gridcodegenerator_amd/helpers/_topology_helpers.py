@@ -105,6 +105,10 @@ def gen_lds_layout(self):
     spw_ = 64 // self.lanes_per_solve
     aba = off["MINV"] + (4 if ((off["MINV"] % 64 == 0) if spw_ <= 2 else ((off["MINV"] // 4) % 2 == 0)) else 0)
     off["KERNELS"]["ABA"] = {"LDS": aba, "OUT": _pad4(n), "SP": off["SP"], "MINV": off["MINV"], "compact": aba + _pad4(n) < (off["TOTAL"] + off["OUT_PER_SOLVE"]) // 2}
+    # crba (tip frame, column walk) touches IN | X | U | T and keeps M where the general slice keeps M^-1: a prefix of the general slice; it stages the dense n^2 record
+    crba = off["MINV"] + n * ld
+    crba += 4 if ((crba % 64 == 0) if spw_ <= 2 else ((crba // 4) % 2 == 0)) else 0
+    off["KERNELS"]["CRBA"] = {"LDS": crba, "OUT": _pad4(n * n), "SP": off["SP"], "MINV": off["MINV"], "compact": False}
     if getattr(self, "branch_components", False) and not self.tuning["out_half"]:
         from ..algorithms._branch_frame_gradient import branch_spare_in_image
         P = self.branch_plan
@@ -118,6 +122,10 @@ def gen_lds_layout(self):
         mv = sp0 + sp_len(n * ld)
         # (n^2 a multiple of 4: the kernel gathers its output record straight from s_Minv with 16-byte stores, no second staging copy)
         off["KERNELS"]["MINV"] = {"LDS": fix(mv + n * ld), "OUT": 0 if (n * n) % 4 == 0 else _pad4(n * n), "SP": sp0, "MINV": mv, "compact": True}
+        # crba of branch-component robots: direct_minv's compact slice (IN | X | path axes | M), with the dense record staged behind the slices
+        off["KERNELS"]["CRBA"] = dict(off["KERNELS"]["MINV"], OUT=_pad4(n * n))
+    elif getattr(self, "branch_components", False):
+        off["KERNELS"]["CRBA"] = dict(generic, OUT=_pad4(n * n))  # (the path-axis scratch lies outside the prefix)
     return off
 
 

@@ -178,11 +178,13 @@ class GridLibrary:
 
     def host_f64(self, algorithm, *arrays, gravity=9.81):
         """T = double host-buffer entry points: algorithm in {inverse_dynamics, inverse_dynamics_gradient, direct_minv, forward_dynamics, aba,
-        idsva_so, fdsva_so, end_effector_pose, end_effector_pose_gradient, end_effector_pose_gradient_hessian}; arrays as for the float methods
+        idsva_so, fdsva_so, end_effector_pose, end_effector_pose_gradient, end_effector_pose_gradient_hessian, crba}; arrays as for the float methods
         (q_qd[, qdd] / q / q_qd_u[, qdd]) in float64."""
         n = self.n
         if algorithm in ("end_effector_pose", "end_effector_pose_gradient", "end_effector_pose_gradient_hessian"):
             return self._ee_host(("end_effector_pose", "end_effector_pose_gradient", "end_effector_pose_gradient_hessian").index(algorithm), arrays[0], np.float64)
+        if algorithm == "crba":
+            return self._crba_host(arrays[0], np.float64)
         P = lambda a: ctypes.c_void_p(None) if a is None else ctypes.c_void_p(a.ctypes.data)
         # same column rules as the float methods; entry points without a stride argument read exactly 3n values per solve
         first = {"inverse_dynamics": (2 * n, 3 * n), "inverse_dynamics_gradient": (2 * n, 3 * n), "direct_minv": (n, 2 * n, 3 * n)}.get(algorithm, 3 * n)
@@ -246,6 +248,18 @@ class GridLibrary:
         out = np.empty((x.shape[0], n * n), dtype=np.float32)
         self._check(self.lib.grid_direct_minv_host(self.handle, _ptr(x), ctypes.c_int(x.shape[1]), ctypes.c_int(x.shape[0]), _ptr(out)))
         return out
+
+    # ---- joint-space inertia matrix: (N, n | 2n | 3n) rows whose first n values are q -> (N, n*n) dense symmetric M
+    def _crba_host(self, q, dtype):
+        n = self.n
+        x = self._host_in(q, (n, 2 * n, 3 * n), "q", dtype)
+        out = np.empty((x.shape[0], n * n), dtype=dtype)
+        fn = self.lib.grid_crba_host_f64 if dtype == np.float64 else self.lib.grid_crba_host
+        self._check(fn(self.handle, ctypes.c_void_p(x.ctypes.data), ctypes.c_int(x.shape[1]), ctypes.c_int(x.shape[0]), ctypes.c_void_p(out.ctypes.data)))
+        return out
+
+    def crba_host(self, q):
+        return self._crba_host(q, np.float32)
 
     def forward_dynamics_host(self, q_qd_u, gravity=9.81, aba=False):
         x = self._host_in(q_qd_u, 3 * self.n, "q_qd_u")
@@ -359,6 +373,10 @@ class GridLibrary:
 
     def direct_minv_device(self, d_q, N, d_Minv, stride=None, stream=0):
         self._check(self.lib.grid_direct_minv_device(self.handle, _ptr(d_q), ctypes.c_int(stride or 3 * self.n), ctypes.c_int(N), _ptr(d_Minv), ctypes.c_void_p(stream)))
+
+    def crba_device(self, d_q, N, d_M, stride=None, stream=0):
+        """stride defaults to 3n (q_qd_u rows), as for direct_minv_device; the kernel reads the first n values of every row"""
+        self._check(self.lib.grid_crba_device(self.handle, _ptr(d_q), ctypes.c_int(stride or 3 * self.n), ctypes.c_int(N), _ptr(d_M), ctypes.c_void_p(stream)))
 
     def forward_dynamics_device(self, d_q_qd_u, N, d_qdd, stride=None, gravity=9.81, stream=0):
         self._check(self.lib.grid_forward_dynamics_device(self.handle, _ptr(d_q_qd_u), ctypes.c_int(stride or 3 * self.n), ctypes.c_int(N),

@@ -172,6 +172,17 @@ int grid_end_effector_pose_host_f64(grid_handle *h, const double *h_q, int strid
 int grid_end_effector_pose_gradient_host_f64(grid_handle *h, const double *h_q, int stride_q, int num_timesteps, double *h_deePos);
 int grid_end_effector_pose_gradient_hessian_host_f64(grid_handle *h, const double *h_q, int stride_q, int num_timesteps, double *h_d2eePos, double *h_deePos);
 
+/* Joint-space inertia matrix M(q) (reference algorithms/_crba.py, emitted by the reference's gen_all_code for every fixed-base robot).
+ * Layout (k = batch index): M[k*n*n + col*n + row], dense (both triangles, structural zeros included); exactly symmetric.
+ * q is the first n values of every row (stride n, 2n: the reference's USE_COMPRESSED_MEM q_qd, 3n: q_qd_u).  No gravity argument: M does not depend on it. */
+/* replaces crba_kernel<T> (reference algorithms/_crba.py: gen_crba_kernel): device buffers, asynchronous on `stream`, nothing allocated; stride_q >= n */
+int grid_crba_device(grid_handle *h, const float *d_q, int stride_q, int num_timesteps, float *d_M, void *stream);
+/* replaces the host wrapper crba<T,USE_COMPRESSED_MEM> (reference algorithms/_crba.py: gen_crba_host): host buffers, synchronous, stride_q in [n, 3n],
+ * num_timesteps <= max_timesteps.  The output is staged in the handle's own d_M buffer, allocated by the first call. */
+int grid_crba_host(grid_handle *h, const float *h_q, int stride_q, int num_timesteps, float *h_M);
+int grid_crba_device_f64(grid_handle *h, const double *d_q, int stride_q, int num_timesteps, double *d_M, void *stream);
+int grid_crba_host_f64(grid_handle *h, const double *h_q, int stride_q, int num_timesteps, double *h_M);
+
 /* in-kernel timing probe: replaces forward_dynamics_gradient_single_timing<T> (reference :236-248); returns microseconds per solve */
 int grid_forward_dynamics_gradient_single_timing(grid_handle *h, const float *h_q_qd_u, int reps, float gravity, float *h_df_du, double *us_per_call);
 

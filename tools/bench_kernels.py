@@ -19,6 +19,7 @@ d_c, d_M, d_g, d_a = E(n), E(n * n), E(2 * n * n), E(n)
 cases = [("inverse_dynamics", lambda: lib.inverse_dynamics_device(d_x, d_qdd, N, d_c, stream=st)),
          ("inverse_dynamics_gradient", lambda: lib.inverse_dynamics_gradient_device(d_x, d_qdd, N, d_g, stream=st)),
          ("direct_minv", lambda: lib.direct_minv_device(d_x, N, d_M, stream=st)),
+         ("crba", lambda: lib.crba_device(d_x, N, d_M, stride=3 * n, stream=st)),
          ("forward_dynamics", lambda: lib.forward_dynamics_device(d_x, N, d_a, stream=st)),
          ("aba", lambda: lib.aba_device(d_x, N, d_a, stream=st)),
          ("forward_dynamics_gradient", lambda: lib.forward_dynamics_gradient_device(d_x, N, d_g, stream=st))]
