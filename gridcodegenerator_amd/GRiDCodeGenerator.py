@@ -158,7 +158,10 @@ class GRiDCodeGenerator:
     # NumPy debug helpers with the reference's names and signatures (reference GRiDCodeGenerator.py:50-51, README "Additional Features")
     from ._test import test_rnea, test_minv, test_rnea_grad, test_fd_grad
     from ._test import test_end_effector_pose, test_end_effector_pose_gradient, test_end_effector_pose_hessian
-    from ._test import test_crba
+    # fused multi-step rollout: aba + symplectic Euler, state resident in LDS (no counterpart in the reference)
+    from .algorithms import gen_rollout_constants, gen_rollout_step_helper, gen_rollout_device, gen_rollout_kernel, gen_rollout_reserve, gen_rollout_host, gen_rollout
+
+    from ._test import test_crba, test_rollout
 
     def __init__(self, robotObj, DEBUG_MODE=False, NEED_PRINT_MAT=False, USE_DYNAMIC_SHARED_MEM=True, FILE_NAMESPACE="grid", COLS_PER_LANE=None, tuning=None):
         if not USE_DYNAMIC_SHARED_MEM:
@@ -390,6 +393,8 @@ class GRiDCodeGenerator:
                                  "    T *d_eePos;", "    T *d_deePos;", "    T *d_d2eePos;", "    T *d_idsva_so;", "    T *d_df2;",
                                  "    // CPU OUTPUTS", "    T *h_c;", "    T *h_Minv;", "    T *h_qdd;", "    T *h_M;", "    T *h_dc_du;", "    T *h_df_du;",
                                  "    T *h_eePos;", "    T *h_deePos;", "    T *h_d2eePos;", "    T *h_idsva_so;", "    T *h_df2;",
+                                 "    // ROLLOUT (no counterpart in the reference's struct; reserved by rollout_reserve, not by init_gridData)",
+                                 "    T *d_u_traj;", "    T *d_x_traj;", "    T *h_u_traj;", "    T *h_x_traj;",
                                  "};"])
 
     def gen_init_gridData(self):
@@ -397,7 +402,8 @@ class GRiDCodeGenerator:
                ("d_Minv", "NUM_JOINTS*NUM_JOINTS"), ("d_qdd", "NUM_JOINTS"), ("d_dc_du", "NUM_JOINTS*2*NUM_JOINTS"), ("d_df_du", "NUM_JOINTS*2*NUM_JOINTS")]
         host = [("h_q_qd_u", "3*NUM_JOINTS"), ("h_q_qd", "2*NUM_JOINTS"), ("h_q", "NUM_JOINTS"), ("h_c", "NUM_JOINTS"),
                 ("h_Minv", "NUM_JOINTS*NUM_JOINTS"), ("h_qdd", "NUM_JOINTS"), ("h_dc_du", "NUM_JOINTS*2*NUM_JOINTS"), ("h_df_du", "NUM_JOINTS*2*NUM_JOINTS")]
-        unused = ["d_M", "d_eePos", "d_deePos", "d_d2eePos", "d_idsva_so", "d_df2", "h_M", "h_eePos", "h_deePos", "h_d2eePos", "h_idsva_so", "h_df2"]
+        unused = ["d_M", "d_eePos", "d_deePos", "d_d2eePos", "d_idsva_so", "d_df2", "h_M", "h_eePos", "h_deePos", "h_d2eePos", "h_idsva_so", "h_df2",
+                  "d_u_traj", "d_x_traj", "h_u_traj", "h_x_traj"]
         if self.gen_idsva_so_available():
             dev += [("d_idsva_so", "4*NUM_JOINTS*NUM_JOINTS*NUM_JOINTS"), ("d_df2", "4*NUM_JOINTS*NUM_JOINTS*NUM_JOINTS")]
             host += [("h_idsva_so", "4*NUM_JOINTS*NUM_JOINTS*NUM_JOINTS"), ("h_df2", "4*NUM_JOINTS*NUM_JOINTS*NUM_JOINTS")]
@@ -461,6 +467,7 @@ class GRiDCodeGenerator:
                                  "// kinematics buffers: allocated by the first end_effector_pose* host call (grid_ee_reserve)",
                                  "grid_ee_release(&hd_data->d_eePos, &hd_data->h_eePos); grid_ee_release(&hd_data->d_deePos, &hd_data->h_deePos); grid_ee_release(&hd_data->d_d2eePos, &hd_data->h_d2eePos);",
                                  "grid_ee_release(&hd_data->d_M, &hd_data->h_M); // (allocated by the first crba host call)",
+                                 "grid_ee_release(&hd_data->d_u_traj, &hd_data->h_u_traj); grid_ee_release(&hd_data->d_x_traj, &hd_data->h_x_traj); // (allocated by rollout_reserve)",
                                  "free(hd_data);",
                                  "for(int i=0; i<" + str(MAX_STREAMS) + "; i++){gpuErrchk(hipStreamDestroy(streams[i]));} free(streams);"])
         self.gen_add_end_function()
@@ -535,6 +542,7 @@ class GRiDCodeGenerator:
         if not self.nested:
             self.gen_eepose_and_derivatives(use_thread_group)  # (outer namespace only: the nested `wide` instance carries the second-order kernels alone)
             self.gen_crba(use_thread_group)  # (outer namespace only, after the kinematics: its host wrappers reserve d_M / h_M with grid_ee_reserve)
+            self.gen_rollout(use_thread_group)  # (outer namespace only; rollout_reserve uses grid_ee_reserve too)
         if not self.nested:
             self.gen_init_close_grid()
 
@@ -601,6 +609,12 @@ class GRiDCodeGenerator:
                       "    __device__ crba_device<T>(T *s_M, const T *s_q, T *s_work, const robotModel<T> *d_robotModel, const int lane[, const int off_sp])",
                       "    __global__ crba_kernel<T>(T *d_M, const T *d_q_qd, const int stride_q_qd, const robotModel<T> *d_robotModel, const T gravity, const int NUM_TIMESTEPS)",
                       "    __host__   crba<T,USE_COMPRESSED_MEM=false>(gridData<T> *hd_data, const robotModel<T> *d_robotModel, const T gravity, const int num_timesteps, const dim3 block_dimms, const dim3 thread_dimms, hipStream_t *streams)",
+                      "",
+                      "    fused rollout, no counterpart in the reference: num_steps steps of aba + semi-implicit Euler per solve in one launch (time-major u (T, N, n), traj (T+1, N, 2n), xT (N, 2n)):",
+                      "    __device__ rollout_device<T>(T *s_q, T *s_qd, const T *s_tau, T *s_qdd, T *s_work, const robotModel<T> *d_robotModel, const T dt, const T gravity, const int lane)",
+                      "    __global__ rollout_kernel<T>(T *d_traj, T *d_xT, const T *d_x0, const int stride_x0, const T *d_u, const long stride_u_step, const int stride_u_solve, const robotModel<T> *d_robotModel, const T dt, const T gravity, const int NUM_TIMESTEPS, const int NUM_STEPS)",
+                      "    __host__   rollout_reserve<T>(gridData<T> *hd_data, const int num_timesteps, const int num_steps)",
+                      "    __host__   rollout<T>(gridData<T> *hd_data, const robotModel<T> *d_robotModel, const T dt, const T gravity, const int num_timesteps, const int num_steps, const dim3 block_dimms, const dim3 thread_dimms, hipStream_t *streams)",
                       "",
                       "Every host function also exists as NAME_single_timing and NAME_compute_only (no streams argument).",
                       "",

@@ -294,3 +294,19 @@ def test_crba(self, q):
             i = m.parent[i]
             M[i, j] = M[j, i] = F[m.S_index[i]]
     return M
+
+
+def test_rollout(self, q, qd, U, dt, GRAVITY=-9.81):
+    """(T+1, 2n): the states [q_t | qd_t] of T = len(U) steps of semi-implicit (symplectic) Euler from (q, qd) under the controls U (T, n), row 0 being the
+    start: qdd = Minv(q_t) (u_t - c(q_t, qd_t)), qd_{t+1} = qd_t + dt qdd, q_{t+1} = q_t + dt qd_{t+1} (the NEW velocity).  No joint limits, no angle
+    wrapping, no contact: what rollout_kernel computes, in fp64."""
+    q, qd = np.array(q, float), np.array(qd, float)
+    U = np.asarray(U, float).reshape(-1, self.model.n)
+    traj = np.zeros((len(U) + 1, 2 * self.model.n))
+    traj[0] = np.concatenate([q, qd])
+    for t, u in enumerate(U):
+        qdd = test_minv(self, q, True) @ (u - test_rnea(self, q, qd, None, GRAVITY)[0])
+        qd = qd + dt * qdd
+        q = q + dt * qd
+        traj[t + 1] = np.concatenate([q, qd])
+    return traj

@@ -20,3 +20,4 @@ from ._eepose_gradient_hessian import gen_end_effector_pose_inner_temp_mem_size,
     gen_end_effector_pose_gradient_hessian_host, gen_eepose_and_derivatives
 from ._crba import gen_crba_inner_temp_mem_size, gen_crba_inner_function_call, gen_crba_inner, gen_crba_device_temp_mem_size, gen_crba_device, \
     gen_crba_kernel, gen_crba_host, gen_crba_constants, gen_crba
+from ._rollout import gen_rollout_constants, gen_rollout_step_helper, gen_rollout_device, gen_rollout_kernel, gen_rollout_reserve, gen_rollout_host, gen_rollout

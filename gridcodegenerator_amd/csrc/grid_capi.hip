@@ -16,6 +16,7 @@ struct grid_capi_error {
 #include "grid.cuh"
 #include "grid_capi.h"
 
+#include <limits.h>
 #include <string.h>
 
 #include <mutex>
@@ -33,6 +34,7 @@ struct grid_typed {
     grid::robotModel<T> *d_robotModel = nullptr;
     grid::gridData<T> *hd_data = nullptr;
     size_t M_cap = 0;  // elements of hd_data->d_M, the output staging of the crba host entry point (allocated by its first call; no pinned twin)
+    size_t u_traj_cap = 0, x_traj_cap = 0;  // elements of hd_data->d_u_traj / d_x_traj, the staging of the rollout host entry point (same rules)
 };
 
 // staging of the kinematics host entry points (grid_end_effector_pose*_host): allocated by the first kinematics call on a handle, never by grid_init,
@@ -698,6 +700,87 @@ static int crba_host(grid_handle *h, const T *h_q, int stride, int N, T *h_M) {
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- fused rollout
+// u: element (t, k, j) at d_u[t*stride_u_step + k*stride_u_solve + j].  Every solve's row must lie inside its step and the steps must not overlap
+// (a smaller or negative stride would read before / past the caller's buffer); stride_u_solve == 0 is the one legal alias: one sequence for all solves.
+static int check_rollout_strides(int stride_x0, long stride_u_step, int stride_u_solve, int N, int num_steps) {
+    const int n = (int)grid::NUM_JOINTS;
+    if (stride_x0 < 2 * n) {
+        snprintf(g_err, sizeof(g_err), "stride_x0 %d is smaller than the %d values [q | qd] the kernel reads per solve", stride_x0, 2 * n);
+        return (int)hipErrorInvalidValue;
+    }
+    if (stride_u_solve != 0 && stride_u_solve < n) {
+        snprintf(g_err, sizeof(g_err), "stride_u_solve %d must be 0 (one control sequence for all solves) or at least the %d controls of a solve", stride_u_solve, n);
+        return (int)hipErrorInvalidValue;
+    }
+    const long span = stride_u_solve == 0 ? (long)n : (long)(N - 1) * stride_u_solve + n;  // what one step touches
+    if (span > (long)INT_MAX) return fail_msg(hipErrorInvalidValue, "stride_u_solve * num_solves exceeds the 32-bit offsets the kernel uses inside one step");
+    if (num_steps > 1 && stride_u_step < span) {
+        snprintf(g_err, sizeof(g_err), "stride_u_step %ld is smaller than the %ld values one step of the control spans", stride_u_step, span);
+        return (int)hipErrorInvalidValue;
+    }
+    return 0;
+}
+
+template <typename T>
+static int rollout_device(grid_handle *h, const T *d_x0, int stride_x0, const T *d_u, long stride_u_step, int stride_u_solve, int N, int num_steps, T dt, T gravity,
+                          T *d_traj, T *d_xT, void *stream) {
+    int rc = check_args(h, N);
+    if (rc) return rc;
+    if (num_steps < 0) return fail_msg(hipErrorInvalidValue, "negative num_steps");
+    if (N == 0) return 0;
+    if (!d_x0 || (num_steps > 0 && !d_u)) return fail_msg(hipErrorInvalidValue, "null input pointer");
+    if (!d_traj && !d_xT) return fail_msg(hipErrorInvalidValue, "null output pointers: at least one of traj and xT must be given");
+    if ((rc = check_rollout_strides(stride_x0, stride_u_step, stride_u_solve, N, num_steps))) return rc;
+    GRID_ON_DEVICE(h);
+    if ((rc = ensure_typed<T>(h))) return rc;
+    launch_cfg c;
+    if ((rc = make_launch<T>(h, N, grid::ROLLOUT_SUGGESTED_THREADS, grid::GRID_MAX_SOLVES_PER_BLOCK, grid::ROLLOUT_LDS_PER_SOLVE, grid::ROLLOUT_OUT_PER_SOLVE, &c))) return rc;
+    hipLaunchKernelGGL((grid::rollout_kernel<T>), c.grid, c.block, c.lds, (hipStream_t)stream, d_traj, d_xT, d_x0, stride_x0, d_u, stride_u_step, stride_u_solve,
+                       typed<T>(h).d_robotModel, dt, gravity, N, num_steps);
+    GRID_TRY(hipGetLastError());
+    return 0;
+}
+
+// Host buffers in, host buffers out, synchronous.  x0 passes through the handle's d_q_qd_u; u and traj / xT do not fit the handle's 3n-per-solve buffers:
+// they are staged in hd_data->d_u_traj / d_x_traj (null after init_gridData, allocated here on first use, grown by longer calls, freed by close_grid).
+template <typename T>
+static int rollout_host(grid_handle *h, const T *h_x0, int stride_x0, const T *h_u, long stride_u_step, int stride_u_solve, int N, int num_steps, T dt, T gravity,
+                        T *h_traj, T *h_xT) {
+    int rc = host_prologue<T>(h, N);
+    if (rc) return rc;
+    if (num_steps < 0) return fail_msg(hipErrorInvalidValue, "negative num_steps");
+    if (N == 0) return 0;
+    if (!h_x0 || (num_steps > 0 && !h_u)) return fail_msg(hipErrorInvalidValue, "null input pointer");
+    if (!h_traj && !h_xT) return fail_msg(hipErrorInvalidValue, "null output pointers: at least one of traj and xT must be given");
+    if ((rc = check_rollout_strides(stride_x0, stride_u_step, stride_u_solve, N, num_steps))) return rc;
+    const size_t n = grid::NUM_JOINTS;
+    if (stride_x0 > 3 * (int)n) return fail_msg(hipErrorInvalidValue, "stride_x0 must be in [2n, 3n] for host buffers");
+    GRID_ON_DEVICE(h);
+    if ((rc = ensure_typed<T>(h))) return rc;
+    grid::gridData<T> *d = typed<T>(h).hd_data;
+    // the control as the caller laid it out: (num_steps - 1) whole steps and the span of the last one
+    const size_t u_span = stride_u_solve == 0 ? n : (size_t)(N - 1) * stride_u_solve + n;
+    const size_t u_count = num_steps > 0 ? (size_t)(num_steps - 1) * (size_t)stride_u_step + u_span : 0;
+    const size_t row = 2 * n * (size_t)N;
+    const size_t x_count = h_traj ? row * ((size_t)num_steps + 1) + (h_xT ? row : 0) : row;
+    {
+        std::lock_guard<std::mutex> lock(h->alloc_lock);
+        if ((rc = ee_grow<T>(&d->d_u_traj, &typed<T>(h).u_traj_cap, u_count > 0 ? u_count : 1))) return rc;
+        if ((rc = ee_grow<T>(&d->d_x_traj, &typed<T>(h).x_traj_cap, x_count))) return rc;
+    }
+    T *d_traj = h_traj ? d->d_x_traj : nullptr;
+    T *d_xT = h_xT ? (h_traj ? d->d_x_traj + row * ((size_t)num_steps + 1) : d->d_x_traj) : nullptr;
+    hipStream_t s = h->streams[0];
+    GRID_H2D(d->d_q_qd_u, h_x0, (size_t)stride_x0 * N);
+    if (u_count > 0) GRID_H2D(d->d_u_traj, h_u, u_count);
+    if ((rc = rollout_device<T>(h, d->d_q_qd_u, stride_x0, d->d_u_traj, stride_u_step, stride_u_solve, N, num_steps, dt, gravity, d_traj, d_xT, (void *)s))) return rc;
+    if (h_traj) GRID_D2H(h_traj, d_traj, row * ((size_t)num_steps + 1));
+    if (h_xT) GRID_D2H(h_xT, d_xT, row);
+    GRID_TRY(hipStreamSynchronize(s));
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- multi-GPU driver
 // One process, G handles (one per GPU): the batch [0, N) is cut into G contiguous ranges of ceil(N/G) solves (SURVEY.md section 8(e),
 // 16 384 total -> 16 384/G per GPU, no collective).  Every device has its own robotModel copy and stream.
@@ -997,6 +1080,22 @@ int grid_crba_device_f64(grid_handle *h, const double *d_q, int stride_q, int nu
 }
 int grid_crba_host_f64(grid_handle *h, const double *h_q, int stride_q, int num_timesteps, double *h_M) {
     GRID_GUARDED(return crba_host<double>(h, h_q, stride_q, num_timesteps, h_M);)
+}
+int grid_rollout_device(grid_handle *h, const float *d_x0, int stride_x0, const float *d_u, long stride_u_step, int stride_u_solve, int num_solves, int num_steps,
+                        float dt, float gravity, float *d_traj, float *d_xT, void *stream) {
+    GRID_GUARDED(return rollout_device<float>(h, d_x0, stride_x0, d_u, stride_u_step, stride_u_solve, num_solves, num_steps, dt, gravity, d_traj, d_xT, stream);)
+}
+int grid_rollout_host(grid_handle *h, const float *h_x0, int stride_x0, const float *h_u, long stride_u_step, int stride_u_solve, int num_solves, int num_steps,
+                      float dt, float gravity, float *h_traj, float *h_xT) {
+    GRID_GUARDED(return rollout_host<float>(h, h_x0, stride_x0, h_u, stride_u_step, stride_u_solve, num_solves, num_steps, dt, gravity, h_traj, h_xT);)
+}
+int grid_rollout_device_f64(grid_handle *h, const double *d_x0, int stride_x0, const double *d_u, long stride_u_step, int stride_u_solve, int num_solves, int num_steps,
+                            double dt, double gravity, double *d_traj, double *d_xT, void *stream) {
+    GRID_GUARDED(return rollout_device<double>(h, d_x0, stride_x0, d_u, stride_u_step, stride_u_solve, num_solves, num_steps, dt, gravity, d_traj, d_xT, stream);)
+}
+int grid_rollout_host_f64(grid_handle *h, const double *h_x0, int stride_x0, const double *h_u, long stride_u_step, int stride_u_solve, int num_solves, int num_steps,
+                          double dt, double gravity, double *h_traj, double *h_xT) {
+    GRID_GUARDED(return rollout_host<double>(h, h_x0, stride_x0, h_u, stride_u_step, stride_u_solve, num_solves, num_steps, dt, gravity, h_traj, h_xT);)
 }
 
 int grid_forward_dynamics_gradient_single_timing(grid_handle *h, const float *h_q_qd_u, int reps, float gravity, float *h_df_du, double *us_per_call) {

@@ -261,6 +261,33 @@ class GridLibrary:
     def crba_host(self, q):
         return self._crba_host(q, np.float32)
 
+    # ---- fused rollout: x0 (N, 2n | 3n) rows starting with [q | qd], u (T, N, n) or one shared sequence (T, n) -> traj (T+1, N, 2n) or xT (N, 2n)
+    def _rollout_host(self, x0, u, dt, final_only, gravity, dtype):
+        n = self.n
+        x = self._host_in(x0, (2 * n, 3 * n), "x0", dtype)
+        N = x.shape[0]
+        uu = np.ascontiguousarray(u, dtype=dtype)
+        if uu.ndim == 2 and uu.shape[1] == n:
+            T, stride_solve, stride_step = uu.shape[0], 0, n
+        elif uu.ndim == 3 and uu.shape[1:] == (N, n):
+            T, stride_solve, stride_step = uu.shape[0], n, N * n
+        else:
+            raise ValueError("u must have shape (T, N, n) or (T, n) with N = %d, n = %d" % (N, n))
+        out = np.empty((N, 2 * n) if final_only else (T + 1, N, 2 * n), dtype=dtype)
+        real = ctypes.c_double if dtype == np.float64 else ctypes.c_float
+        fn = self.lib.grid_rollout_host_f64 if dtype == np.float64 else self.lib.grid_rollout_host
+        null, res = ctypes.c_void_p(None), ctypes.c_void_p(out.ctypes.data)
+        self._check(fn(self.handle, ctypes.c_void_p(x.ctypes.data), ctypes.c_int(x.shape[1]), ctypes.c_void_p(uu.ctypes.data if uu.size else None), ctypes.c_long(stride_step),
+                       ctypes.c_int(stride_solve), ctypes.c_int(N), ctypes.c_int(T), real(dt), real(gravity), null if final_only else res, res if final_only else null))
+        return out
+
+    def rollout_host(self, x0, u, dt, final_only=False, gravity=9.81):
+        """T steps of ABA + semi-implicit Euler in one launch: the float32 trajectory (T+1, N, 2n) with row 0 = x0, or with final_only the last state (N, 2n)"""
+        return self._rollout_host(x0, u, dt, final_only, gravity, np.float32)
+
+    def rollout_host_f64(self, x0, u, dt, final_only=False, gravity=9.81):
+        return self._rollout_host(x0, u, dt, final_only, gravity, np.float64)
+
     def forward_dynamics_host(self, q_qd_u, gravity=9.81, aba=False):
         x = self._host_in(q_qd_u, 3 * self.n, "q_qd_u")
         out = np.empty((x.shape[0], self.n), dtype=np.float32)
@@ -377,6 +404,14 @@ class GridLibrary:
     def crba_device(self, d_q, N, d_M, stride=None, stream=0):
         """stride defaults to 3n (q_qd_u rows), as for direct_minv_device; the kernel reads the first n values of every row"""
         self._check(self.lib.grid_crba_device(self.handle, _ptr(d_q), ctypes.c_int(stride or 3 * self.n), ctypes.c_int(N), _ptr(d_M), ctypes.c_void_p(stream)))
+
+    def rollout_device(self, d_x0, d_u, N, T, dt, d_traj=None, d_xT=None, stride_x0=None, u_shared=False, gravity=9.81, stream=0):
+        """Asynchronous on `stream`, allocates nothing.  d_x0: rows of stride_x0 (default 2n) values starting with [q | qd]; d_u: dense (T, N, n), or with u_shared
+        ONE sequence (T, n) for all solves; d_traj (T+1, N, 2n) and / or d_xT (N, 2n): at least one of them."""
+        n = self.n
+        self._check(self.lib.grid_rollout_device(self.handle, _ptr(d_x0), ctypes.c_int(stride_x0 or 2 * n), _ptr(d_u), ctypes.c_long(n if u_shared else N * n),
+                                                 ctypes.c_int(0 if u_shared else n), ctypes.c_int(N), ctypes.c_int(T), ctypes.c_float(dt), ctypes.c_float(gravity),
+                                                 _ptr(d_traj), _ptr(d_xT), ctypes.c_void_p(stream)))
 
     def forward_dynamics_device(self, d_q_qd_u, N, d_qdd, stride=None, gravity=9.81, stream=0):
         self._check(self.lib.grid_forward_dynamics_device(self.handle, _ptr(d_q_qd_u), ctypes.c_int(stride or 3 * self.n), ctypes.c_int(N),

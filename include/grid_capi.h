@@ -183,6 +183,28 @@ int grid_crba_host(grid_handle *h, const float *h_q, int stride_q, int num_times
 int grid_crba_device_f64(grid_handle *h, const double *d_q, int stride_q, int num_timesteps, double *d_M, void *stream);
 int grid_crba_host_f64(grid_handle *h, const double *h_q, int stride_q, int num_timesteps, double *h_M);
 
+/* Fused rollout: num_steps steps of ABA forward dynamics + semi-implicit (symplectic) Euler for num_solves independent trajectories in ONE launch, the
+ * state resident in LDS between the steps.  The reference has no counterpart (its user launches aba_kernel once per step and integrates in between).
+ *   qdd = ABA(q_t, qd_t, u_t);  qd_{t+1} = qd_t + dt*qdd;  q_{t+1} = q_t + dt*qd_{t+1}   (no joint limits, no angle wrapping, no contact)
+ * Layouts (n joints, k = solve, t = step; time-major):
+ *   x0    rows of stride_x0 >= 2n values whose first 2n are [q | qd] (the 3n q_qd_u rows of the other entry points are accepted as they are)
+ *   u     element (t, k, j) at u[t*stride_u_step + k*stride_u_solve + j]; dense (num_steps, num_solves, n): stride_u_solve = n, stride_u_step = num_solves*n;
+ *         stride_u_solve = 0: ONE sequence (num_steps, n) for all solves.  Otherwise stride_u_solve >= n, and stride_u_step covers what one step spans
+ *   traj  (num_steps+1, num_solves, 2n), traj[t][k] = [q_t | qd_t], row 0 is x0; may be NULL: nothing is written during the steps
+ *   xT    (num_solves, 2n), the final state; may be NULL.  At least one of traj and xT must be given.
+ * num_steps == 0 copies x0 to the outputs.  Negative counts, NULL inputs, both outputs NULL and bad strides are errors (grid_last_error). */
+/* no counterpart in the reference (launches rollout_kernel<T>): device buffers, asynchronous on `stream`, nothing allocated */
+int grid_rollout_device(grid_handle *h, const float *d_x0, int stride_x0, const float *d_u, long stride_u_step, int stride_u_solve, int num_solves, int num_steps,
+                        float dt, float gravity, float *d_traj, float *d_xT, void *stream);
+/* no counterpart in the reference: host buffers, synchronous, stride_x0 in [2n, 3n], num_solves <= max_timesteps.  u and traj / xT are staged in device
+ * buffers of the handle that the first call allocates and longer calls grow; grid_close frees them. */
+int grid_rollout_host(grid_handle *h, const float *h_x0, int stride_x0, const float *h_u, long stride_u_step, int stride_u_solve, int num_solves, int num_steps,
+                      float dt, float gravity, float *h_traj, float *h_xT);
+int grid_rollout_device_f64(grid_handle *h, const double *d_x0, int stride_x0, const double *d_u, long stride_u_step, int stride_u_solve, int num_solves, int num_steps,
+                            double dt, double gravity, double *d_traj, double *d_xT, void *stream);
+int grid_rollout_host_f64(grid_handle *h, const double *h_x0, int stride_x0, const double *h_u, long stride_u_step, int stride_u_solve, int num_solves, int num_steps,
+                          double dt, double gravity, double *h_traj, double *h_xT);
+
 /* in-kernel timing probe: replaces forward_dynamics_gradient_single_timing<T> (reference :236-248); returns microseconds per solve */
 int grid_forward_dynamics_gradient_single_timing(grid_handle *h, const float *h_q_qd_u, int reps, float gravity, float *h_df_du, double *us_per_call);
 
