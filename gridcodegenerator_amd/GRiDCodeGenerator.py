@@ -162,6 +162,10 @@ class GRiDCodeGenerator:
     from .algorithms import gen_rollout_constants, gen_rollout_step_helper, gen_rollout_device, gen_rollout_kernel, gen_rollout_reserve, gen_rollout_host, gen_rollout
 
     from ._test import test_crba, test_rollout
+    # linearised rollout: the trajectory and the Jacobians of the dynamics along it in one launch (no counterpart in the reference)
+    from .algorithms import gen_rollout_linearized_layout, gen_rollout_linearized_constants, gen_rollout_linearized_device, gen_rollout_linearized_kernel, \
+        gen_rollout_linearized_reserve, gen_rollout_linearized_host, gen_rollout_linearized
+    from ._test import test_rollout_linearized
 
     def __init__(self, robotObj, DEBUG_MODE=False, NEED_PRINT_MAT=False, USE_DYNAMIC_SHARED_MEM=True, FILE_NAMESPACE="grid", COLS_PER_LANE=None, tuning=None):
         if not USE_DYNAMIC_SHARED_MEM:
@@ -395,6 +399,8 @@ class GRiDCodeGenerator:
                                  "    T *h_eePos;", "    T *h_deePos;", "    T *h_d2eePos;", "    T *h_idsva_so;", "    T *h_df2;",
                                  "    // ROLLOUT (no counterpart in the reference's struct; reserved by rollout_reserve, not by init_gridData)",
                                  "    T *d_u_traj;", "    T *d_x_traj;", "    T *h_u_traj;", "    T *h_x_traj;",
+                                 "    // LINEARISED ROLLOUT (reserved by rollout_linearized_reserve, not by init_gridData)",
+                                 "    T *d_fx_traj;", "    T *d_fu_traj;", "    T *h_fx_traj;", "    T *h_fu_traj;",
                                  "};"])
 
     def gen_init_gridData(self):
@@ -403,7 +409,7 @@ class GRiDCodeGenerator:
         host = [("h_q_qd_u", "3*NUM_JOINTS"), ("h_q_qd", "2*NUM_JOINTS"), ("h_q", "NUM_JOINTS"), ("h_c", "NUM_JOINTS"),
                 ("h_Minv", "NUM_JOINTS*NUM_JOINTS"), ("h_qdd", "NUM_JOINTS"), ("h_dc_du", "NUM_JOINTS*2*NUM_JOINTS"), ("h_df_du", "NUM_JOINTS*2*NUM_JOINTS")]
         unused = ["d_M", "d_eePos", "d_deePos", "d_d2eePos", "d_idsva_so", "d_df2", "h_M", "h_eePos", "h_deePos", "h_d2eePos", "h_idsva_so", "h_df2",
-                  "d_u_traj", "d_x_traj", "h_u_traj", "h_x_traj"]
+                  "d_u_traj", "d_x_traj", "h_u_traj", "h_x_traj", "d_fx_traj", "d_fu_traj", "h_fx_traj", "h_fu_traj"]
         if self.gen_idsva_so_available():
             dev += [("d_idsva_so", "4*NUM_JOINTS*NUM_JOINTS*NUM_JOINTS"), ("d_df2", "4*NUM_JOINTS*NUM_JOINTS*NUM_JOINTS")]
             host += [("h_idsva_so", "4*NUM_JOINTS*NUM_JOINTS*NUM_JOINTS"), ("h_df2", "4*NUM_JOINTS*NUM_JOINTS*NUM_JOINTS")]
@@ -468,6 +474,7 @@ class GRiDCodeGenerator:
                                  "grid_ee_release(&hd_data->d_eePos, &hd_data->h_eePos); grid_ee_release(&hd_data->d_deePos, &hd_data->h_deePos); grid_ee_release(&hd_data->d_d2eePos, &hd_data->h_d2eePos);",
                                  "grid_ee_release(&hd_data->d_M, &hd_data->h_M); // (allocated by the first crba host call)",
                                  "grid_ee_release(&hd_data->d_u_traj, &hd_data->h_u_traj); grid_ee_release(&hd_data->d_x_traj, &hd_data->h_x_traj); // (allocated by rollout_reserve)",
+                                 "grid_ee_release(&hd_data->d_fx_traj, &hd_data->h_fx_traj); grid_ee_release(&hd_data->d_fu_traj, &hd_data->h_fu_traj); // (allocated by rollout_linearized_reserve)",
                                  "free(hd_data);",
                                  "for(int i=0; i<" + str(MAX_STREAMS) + "; i++){gpuErrchk(hipStreamDestroy(streams[i]));} free(streams);"])
         self.gen_add_end_function()
@@ -543,6 +550,7 @@ class GRiDCodeGenerator:
             self.gen_eepose_and_derivatives(use_thread_group)  # (outer namespace only: the nested `wide` instance carries the second-order kernels alone)
             self.gen_crba(use_thread_group)  # (outer namespace only, after the kinematics: its host wrappers reserve d_M / h_M with grid_ee_reserve)
             self.gen_rollout(use_thread_group)  # (outer namespace only; rollout_reserve uses grid_ee_reserve too)
+            self.gen_rollout_linearized(use_thread_group)  # (after rollout: it calls grid_symplectic_euler_step and rollout_reserve)
         if not self.nested:
             self.gen_init_close_grid()
 
@@ -615,6 +623,12 @@ class GRiDCodeGenerator:
                       "    __global__ rollout_kernel<T>(T *d_traj, T *d_xT, const T *d_x0, const int stride_x0, const T *d_u, const long stride_u_step, const int stride_u_solve, const robotModel<T> *d_robotModel, const T dt, const T gravity, const int NUM_TIMESTEPS, const int NUM_STEPS)",
                       "    __host__   rollout_reserve<T>(gridData<T> *hd_data, const int num_timesteps, const int num_steps)",
                       "    __host__   rollout<T>(gridData<T> *hd_data, const robotModel<T> *d_robotModel, const T dt, const T gravity, const int num_timesteps, const int num_steps, const dim3 block_dimms, const dim3 thread_dimms, hipStream_t *streams)",
+                      "",
+                      "    linearised rollout, no counterpart in the reference: rollout + the Jacobians of the dynamics at every step (fx (T, N, 2n^2) = df_du records, fu (T, N, n^2) = dense M^-1):",
+                      "    __device__ rollout_linearized_device<T>(T *s_fx, T *s_q, T *s_qd, const T *s_tau, T *s_work, const robotModel<T> *d_robotModel, const T dt, const T gravity, const int lane, const bool want_fu = true)",
+                      "    __global__ rollout_linearized_kernel<T>(T *d_traj, T *d_xT, T *d_fx, T *d_fu, const T *d_x0, const int stride_x0, const T *d_u, const long stride_u_step, const int stride_u_solve, const robotModel<T> *d_robotModel, const T dt, const T gravity, const int NUM_TIMESTEPS, const int NUM_STEPS)",
+                      "    __host__   rollout_linearized_reserve<T>(gridData<T> *hd_data, const int num_timesteps, const int num_steps)",
+                      "    __host__   rollout_linearized<T>(gridData<T> *hd_data, const robotModel<T> *d_robotModel, const T dt, const T gravity, const int num_timesteps, const int num_steps, const dim3 block_dimms, const dim3 thread_dimms, hipStream_t *streams)",
                       "",
                       "Every host function also exists as NAME_single_timing and NAME_compute_only (no streams argument).",
                       "",

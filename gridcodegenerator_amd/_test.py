@@ -310,3 +310,17 @@ def test_rollout(self, q, qd, U, dt, GRAVITY=-9.81):
         q = q + dt * qd
         traj[t + 1] = np.concatenate([q, qd])
     return traj
+
+
+def test_rollout_linearized(self, q, qd, U, dt, GRAVITY=-9.81):
+    """(states (T+1, 2n), fx (T, 2n^2), fu (T, n^2)): test_rollout's states and, at every (q_t, qd_t, u_t) along them, the records rollout_linearized_kernel
+    writes: fx = test_fd_grad (n x 2n, stored fx[col*n + row]) and fu = d qdd/du = test_minv (dense, symmetric, fu[col*n + row]), in fp64."""
+    n = self.model.n
+    U = np.asarray(U, float).reshape(-1, n)
+    traj = test_rollout(self, q, qd, U, dt, GRAVITY)
+    fx, fu = np.zeros((len(U), 2 * n * n)), np.zeros((len(U), n * n))
+    for t, u in enumerate(U):
+        fx[t] = test_fd_grad(self, traj[t, :n], traj[t, n:], u, GRAVITY).T.reshape(-1)
+        Minv = test_minv(self, traj[t, :n], True)
+        fu[t] = (0.5 * (Minv + Minv.T)).T.reshape(-1)
+    return traj, fx, fu

@@ -35,6 +35,7 @@ struct grid_typed {
     grid::gridData<T> *hd_data = nullptr;
     size_t M_cap = 0;  // elements of hd_data->d_M, the output staging of the crba host entry point (allocated by its first call; no pinned twin)
     size_t u_traj_cap = 0, x_traj_cap = 0;  // elements of hd_data->d_u_traj / d_x_traj, the staging of the rollout host entry point (same rules)
+    size_t fx_traj_cap = 0, fu_traj_cap = 0;  // elements of hd_data->d_fx_traj / d_fu_traj, the Jacobian staging of the linearised rollout host entry point (same rules)
 };
 
 // staging of the kinematics host entry points (grid_end_effector_pose*_host): allocated by the first kinematics call on a handle, never by grid_init,
@@ -781,6 +782,84 @@ static int rollout_host(grid_handle *h, const T *h_x0, int stride_x0, const T *h
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- linearised rollout
+// The rollout above plus, per step, the Jacobian records fx (2n^2) and fu (n^2).  Same validation; at least one of the four outputs must be given.
+template <typename T>
+static int rollout_linearized_device(grid_handle *h, const T *d_x0, int stride_x0, const T *d_u, long stride_u_step, int stride_u_solve, int N, int num_steps, T dt, T gravity,
+                                     T *d_traj, T *d_xT, T *d_fx, T *d_fu, void *stream) {
+    int rc = check_args(h, N);
+    if (rc) return rc;
+    if (num_steps < 0) return fail_msg(hipErrorInvalidValue, "negative num_steps");
+    if (N == 0) return 0;
+    if (!d_x0 || (num_steps > 0 && !d_u)) return fail_msg(hipErrorInvalidValue, "null input pointer");
+    if (!d_traj && !d_xT && !d_fx && !d_fu) return fail_msg(hipErrorInvalidValue, "null output pointers: at least one of traj, xT, fx and fu must be given");
+    if ((rc = check_rollout_strides(stride_x0, stride_u_step, stride_u_solve, N, num_steps))) return rc;
+    if (num_steps == 0 && !d_traj && !d_xT) return 0;  // (no step: no Jacobian is written)
+    GRID_ON_DEVICE(h);
+    if ((rc = ensure_typed<T>(h))) return rc;
+    launch_cfg c;
+    if ((rc = make_launch<T>(h, N, grid::ROLLOUT_LIN_SUGGESTED_THREADS, grid::GRID_MAX_SOLVES_PER_BLOCK, grid::ROLLOUT_LIN_LDS_PER_SOLVE, grid::ROLLOUT_LIN_OUT_PER_SOLVE, &c))) return rc;
+    hipLaunchKernelGGL((grid::rollout_linearized_kernel<T>), c.grid, c.block, c.lds, (hipStream_t)stream, d_traj, d_xT, d_fx, d_fu, d_x0, stride_x0, d_u, stride_u_step,
+                       stride_u_solve, typed<T>(h).d_robotModel, dt, gravity, N, num_steps);
+    GRID_TRY(hipGetLastError());
+    return 0;
+}
+
+// Host buffers in, host buffers out, synchronous.  x0 passes through the handle's d_q_qd_u, u and traj / xT through d_u_traj / d_x_traj like rollout_host, the
+// Jacobians through hd_data->d_fx_traj / d_fu_traj (null after init_gridData, allocated here on first use, grown by longer calls, freed by close_grid).
+// No staged output may exceed GRID_ROLLOUT_LIN_HOST_CAP_BYTES: such a call is refused before anything is allocated or copied.
+template <typename T>
+static int rollout_linearized_host(grid_handle *h, const T *h_x0, int stride_x0, const T *h_u, long stride_u_step, int stride_u_solve, int N, int num_steps, T dt, T gravity,
+                                   T *h_traj, T *h_xT, T *h_fx, T *h_fu) {
+    int rc = host_prologue<T>(h, N);
+    if (rc) return rc;
+    if (num_steps < 0) return fail_msg(hipErrorInvalidValue, "negative num_steps");
+    if (N == 0) return 0;
+    if (!h_x0 || (num_steps > 0 && !h_u)) return fail_msg(hipErrorInvalidValue, "null input pointer");
+    if (!h_traj && !h_xT && !h_fx && !h_fu) return fail_msg(hipErrorInvalidValue, "null output pointers: at least one of traj, xT, fx and fu must be given");
+    if ((rc = check_rollout_strides(stride_x0, stride_u_step, stride_u_solve, N, num_steps))) return rc;
+    const size_t n = grid::NUM_JOINTS;
+    if (stride_x0 > 3 * (int)n) return fail_msg(hipErrorInvalidValue, "stride_x0 must be in [2n, 3n] for host buffers");
+    const size_t u_span = stride_u_solve == 0 ? n : (size_t)(N - 1) * stride_u_solve + n;
+    const size_t u_count = num_steps > 0 ? (size_t)(num_steps - 1) * (size_t)stride_u_step + u_span : 0;
+    const size_t row = 2 * n * (size_t)N;
+    const size_t x_count = h_traj ? row * ((size_t)num_steps + 1) + (h_xT ? row : 0) : row;
+    const size_t fx_count = h_fx ? 2 * n * n * (size_t)N * (size_t)num_steps : 0;
+    const size_t fu_count = h_fu ? n * n * (size_t)N * (size_t)num_steps : 0;
+    const size_t cap = GRID_ROLLOUT_LIN_HOST_CAP_BYTES / sizeof(T);
+    if (fx_count > cap || fu_count > cap || x_count > cap || u_count > cap) {
+        snprintf(g_err, sizeof(g_err), "rollout_linearized host staging capacity exceeded: %d solves x %d steps need %zu bytes for the largest record, the cap is %zu "
+                 "(split the horizon or use the device entry point)", N, num_steps,
+                 (fx_count > x_count ? (fx_count > u_count ? fx_count : u_count) : (x_count > u_count ? (x_count > fu_count ? x_count : fu_count) : u_count)) * sizeof(T),
+                 (size_t)GRID_ROLLOUT_LIN_HOST_CAP_BYTES);
+        return (int)hipErrorInvalidValue;
+    }
+    GRID_ON_DEVICE(h);
+    if ((rc = ensure_typed<T>(h))) return rc;
+    grid::gridData<T> *d = typed<T>(h).hd_data;
+    {
+        std::lock_guard<std::mutex> lock(h->alloc_lock);
+        if ((rc = ee_grow<T>(&d->d_u_traj, &typed<T>(h).u_traj_cap, u_count > 0 ? u_count : 1))) return rc;
+        if ((rc = ee_grow<T>(&d->d_x_traj, &typed<T>(h).x_traj_cap, x_count))) return rc;
+        if (fx_count > 0 && (rc = ee_grow<T>(&d->d_fx_traj, &typed<T>(h).fx_traj_cap, fx_count))) return rc;
+        if (fu_count > 0 && (rc = ee_grow<T>(&d->d_fu_traj, &typed<T>(h).fu_traj_cap, fu_count))) return rc;
+    }
+    T *d_traj = h_traj ? d->d_x_traj : nullptr;
+    T *d_xT = h_xT ? (h_traj ? d->d_x_traj + row * ((size_t)num_steps + 1) : d->d_x_traj) : nullptr;
+    T *d_fx = fx_count > 0 ? d->d_fx_traj : nullptr, *d_fu = fu_count > 0 ? d->d_fu_traj : nullptr;
+    if (!d_traj && !d_xT && !d_fx && !d_fu) return 0;  // (num_steps == 0 and Jacobians only: there is nothing to write)
+    hipStream_t s = h->streams[0];
+    GRID_H2D(d->d_q_qd_u, h_x0, (size_t)stride_x0 * N);
+    if (u_count > 0) GRID_H2D(d->d_u_traj, h_u, u_count);
+    if ((rc = rollout_linearized_device<T>(h, d->d_q_qd_u, stride_x0, d->d_u_traj, stride_u_step, stride_u_solve, N, num_steps, dt, gravity, d_traj, d_xT, d_fx, d_fu, (void *)s))) return rc;
+    if (h_traj) GRID_D2H(h_traj, d_traj, row * ((size_t)num_steps + 1));
+    if (h_xT) GRID_D2H(h_xT, d_xT, row);
+    if (d_fx) GRID_D2H(h_fx, d_fx, fx_count);
+    if (d_fu) GRID_D2H(h_fu, d_fu, fu_count);
+    GRID_TRY(hipStreamSynchronize(s));
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- multi-GPU driver
 // One process, G handles (one per GPU): the batch [0, N) is cut into G contiguous ranges of ceil(N/G) solves (SURVEY.md section 8(e),
 // 16 384 total -> 16 384/G per GPU, no collective).  Every device has its own robotModel copy and stream.
@@ -1096,6 +1175,22 @@ int grid_rollout_device_f64(grid_handle *h, const double *d_x0, int stride_x0, c
 int grid_rollout_host_f64(grid_handle *h, const double *h_x0, int stride_x0, const double *h_u, long stride_u_step, int stride_u_solve, int num_solves, int num_steps,
                           double dt, double gravity, double *h_traj, double *h_xT) {
     GRID_GUARDED(return rollout_host<double>(h, h_x0, stride_x0, h_u, stride_u_step, stride_u_solve, num_solves, num_steps, dt, gravity, h_traj, h_xT);)
+}
+int grid_rollout_linearized_device(grid_handle *h, const float *d_x0, int stride_x0, const float *d_u, long stride_u_step, int stride_u_solve, int num_solves, int num_steps,
+                                   float dt, float gravity, float *d_traj, float *d_xT, float *d_fx, float *d_fu, void *stream) {
+    GRID_GUARDED(return rollout_linearized_device<float>(h, d_x0, stride_x0, d_u, stride_u_step, stride_u_solve, num_solves, num_steps, dt, gravity, d_traj, d_xT, d_fx, d_fu, stream);)
+}
+int grid_rollout_linearized_host(grid_handle *h, const float *h_x0, int stride_x0, const float *h_u, long stride_u_step, int stride_u_solve, int num_solves, int num_steps,
+                                 float dt, float gravity, float *h_traj, float *h_xT, float *h_fx, float *h_fu) {
+    GRID_GUARDED(return rollout_linearized_host<float>(h, h_x0, stride_x0, h_u, stride_u_step, stride_u_solve, num_solves, num_steps, dt, gravity, h_traj, h_xT, h_fx, h_fu);)
+}
+int grid_rollout_linearized_device_f64(grid_handle *h, const double *d_x0, int stride_x0, const double *d_u, long stride_u_step, int stride_u_solve, int num_solves,
+                                       int num_steps, double dt, double gravity, double *d_traj, double *d_xT, double *d_fx, double *d_fu, void *stream) {
+    GRID_GUARDED(return rollout_linearized_device<double>(h, d_x0, stride_x0, d_u, stride_u_step, stride_u_solve, num_solves, num_steps, dt, gravity, d_traj, d_xT, d_fx, d_fu, stream);)
+}
+int grid_rollout_linearized_host_f64(grid_handle *h, const double *h_x0, int stride_x0, const double *h_u, long stride_u_step, int stride_u_solve, int num_solves,
+                                     int num_steps, double dt, double gravity, double *h_traj, double *h_xT, double *h_fx, double *h_fu) {
+    GRID_GUARDED(return rollout_linearized_host<double>(h, h_x0, stride_x0, h_u, stride_u_step, stride_u_solve, num_solves, num_steps, dt, gravity, h_traj, h_xT, h_fx, h_fu);)
 }
 
 int grid_forward_dynamics_gradient_single_timing(grid_handle *h, const float *h_q_qd_u, int reps, float gravity, float *h_df_du, double *us_per_call) {

@@ -288,6 +288,36 @@ class GridLibrary:
     def rollout_host_f64(self, x0, u, dt, final_only=False, gravity=9.81):
         return self._rollout_host(x0, u, dt, final_only, gravity, np.float64)
 
+    # ---- linearised rollout: the trajectory and, per step, fx = [d qdd/dq | d qdd/dqd] (df_du records) and fu = d qdd/du = M^-1 (dense, symmetric)
+    def _rollout_linearized_host(self, x0, u, dt, gravity, dtype, want=("traj", "fx", "fu")):
+        n = self.n
+        x = self._host_in(x0, (2 * n, 3 * n), "x0", dtype)
+        N = x.shape[0]
+        uu = np.ascontiguousarray(u, dtype=dtype)
+        if uu.ndim == 2 and uu.shape[1] == n:
+            T, stride_solve, stride_step = uu.shape[0], 0, n
+        elif uu.ndim == 3 and uu.shape[1:] == (N, n):
+            T, stride_solve, stride_step = uu.shape[0], n, N * n
+        else:
+            raise ValueError("u must have shape (T, N, n) or (T, n) with N = %d, n = %d" % (N, n))
+        shapes = {"traj": (T + 1, N, 2 * n), "xT": (N, 2 * n), "fx": (T, N, 2 * n * n), "fu": (T, N, n * n)}
+        out = {k: np.empty(shapes[k], dtype=dtype) for k in want}
+        P = lambda k: ctypes.c_void_p(out[k].ctypes.data) if k in out else ctypes.c_void_p(None)
+        real = ctypes.c_double if dtype == np.float64 else ctypes.c_float
+        fn = self.lib.grid_rollout_linearized_host_f64 if dtype == np.float64 else self.lib.grid_rollout_linearized_host
+        self._check(fn(self.handle, ctypes.c_void_p(x.ctypes.data), ctypes.c_int(x.shape[1]), ctypes.c_void_p(uu.ctypes.data if uu.size else None), ctypes.c_long(stride_step),
+                       ctypes.c_int(stride_solve), ctypes.c_int(N), ctypes.c_int(T), real(dt), real(gravity), P("traj"), P("xT"), P("fx"), P("fu")))
+        return tuple(out[k] for k in want)
+
+    def rollout_linearized_host(self, x0, u, dt, gravity=9.81, want=("traj", "fx", "fu")):
+        """T steps of (forward dynamics gradient, M^-1, semi-implicit Euler) in one launch -> (traj (T+1, N, 2n), fx (T, N, 2n^2), fu (T, N, n^2)) in float32;
+        x0, u as for rollout_host.  want: which of "traj", "xT", "fx", "fu" to compute and return, in that order (outputs left out cost no bandwidth;
+        without "fu" the work only M^-1 needs is skipped)."""
+        return self._rollout_linearized_host(x0, u, dt, gravity, np.float32, tuple(want))
+
+    def rollout_linearized_host_f64(self, x0, u, dt, gravity=9.81, want=("traj", "fx", "fu")):
+        return self._rollout_linearized_host(x0, u, dt, gravity, np.float64, tuple(want))
+
     def forward_dynamics_host(self, q_qd_u, gravity=9.81, aba=False):
         x = self._host_in(q_qd_u, 3 * self.n, "q_qd_u")
         out = np.empty((x.shape[0], self.n), dtype=np.float32)
@@ -413,6 +443,14 @@ class GridLibrary:
                                                  ctypes.c_int(0 if u_shared else n), ctypes.c_int(N), ctypes.c_int(T), ctypes.c_float(dt), ctypes.c_float(gravity),
                                                  _ptr(d_traj), _ptr(d_xT), ctypes.c_void_p(stream)))
 
+    def rollout_linearized_device(self, d_x0, d_u, N, T, dt, d_traj=None, d_xT=None, d_fx=None, d_fu=None, stride_x0=None, u_shared=False, gravity=9.81, stream=0):
+        """Asynchronous on `stream`, allocates nothing.  Inputs as rollout_device; outputs (torch tensors or raw addresses, float32, each optional, at least one):
+        d_traj (T+1, N, 2n), d_xT (N, 2n), d_fx (T, N, 2n^2), d_fu (T, N, n^2)."""
+        n = self.n
+        self._check(self.lib.grid_rollout_linearized_device(self.handle, _ptr(d_x0), ctypes.c_int(stride_x0 or 2 * n), _ptr(d_u), ctypes.c_long(n if u_shared else N * n),
+                                                            ctypes.c_int(0 if u_shared else n), ctypes.c_int(N), ctypes.c_int(T), ctypes.c_float(dt), ctypes.c_float(gravity),
+                                                            _ptr(d_traj), _ptr(d_xT), _ptr(d_fx), _ptr(d_fu), ctypes.c_void_p(stream)))
+
     def forward_dynamics_device(self, d_q_qd_u, N, d_qdd, stride=None, gravity=9.81, stream=0):
         self._check(self.lib.grid_forward_dynamics_device(self.handle, _ptr(d_q_qd_u), ctypes.c_int(stride or 3 * self.n), ctypes.c_int(N),
                                                           ctypes.c_float(gravity), _ptr(d_qdd), ctypes.c_void_p(stream)))
@@ -461,6 +499,36 @@ class MultiGpuGrid:
     def close(self):
         for p in self.parts:
             p.close()
+
+
+def discrete_jacobians(fx, fu, dt):
+    """Jacobians of ONE step x_{t+1} = step(x_t, u_t), x = [q; qd], of the semi-implicit Euler integrator of rollout / rollout_linearized, from the
+    continuous-time records: fx (..., 2n^2) = [Fq | Fv] stored [col*n + row], fu (..., n^2) = M^-1.  Returns row-major matrices
+        A (..., 2n, 2n) = [[I + dt^2 Fq, dt (I + dt Fv)], [dt Fq, I + dt Fv]],   B (..., 2n, n) = [[dt^2 fu], [dt fu]]
+    NumPy in -> NumPy out; torch in -> torch out on the same device.  Nothing but this formula: no dynamics is evaluated."""
+    n2 = fu.shape[-1]
+    n = int(round(n2 ** 0.5))
+    if n * n != n2 or fx.shape[-1] != 2 * n2 or tuple(fx.shape[:-1]) != tuple(fu.shape[:-1]):
+        raise ValueError("fx must have shape (..., 2n^2) and fu (..., n^2) with the same leading dimensions")
+    lead = tuple(fu.shape[:-1])
+    if isinstance(fx, np.ndarray):
+        F = np.swapaxes(fx.reshape(lead + (2 * n, n)), -1, -2)  # (..., row, col): n x 2n
+        M = np.swapaxes(fu.reshape(lead + (n, n)), -1, -2)
+        eye = np.eye(n, dtype=fx.dtype)
+        cat = np.concatenate
+    else:
+        import torch
+
+        F = fx.reshape(lead + (2 * n, n)).transpose(-1, -2)
+        M = fu.reshape(lead + (n, n)).transpose(-1, -2)
+        eye = torch.eye(n, dtype=fx.dtype, device=fx.device)
+        cat = lambda parts, axis: torch.cat(parts, dim=axis)
+    Fq, Fv = F[..., :n], F[..., n:]
+    low_q, low_v = dt * Fq, eye + dt * Fv          # d qd_{t+1} / d q_t, / d qd_t
+    top_q, top_v = eye + dt * low_q, dt * low_v    # q_{t+1} = q_t + dt qd_{t+1}
+    A = cat([cat([top_q, top_v], -1), cat([low_q, low_v], -1)], -2)
+    B = cat([(dt * dt) * M, dt * M], -2)
+    return A, B
 
 
 def load(robot_name, device=0, max_timesteps=16384, build_dir=None):

@@ -205,6 +205,30 @@ int grid_rollout_device_f64(grid_handle *h, const double *d_x0, int stride_x0, c
 int grid_rollout_host_f64(grid_handle *h, const double *h_x0, int stride_x0, const double *h_u, long stride_u_step, int stride_u_solve, int num_solves, int num_steps,
                           double dt, double gravity, double *h_traj, double *h_xT);
 
+/* Linearised rollout: the fused rollout AND the Jacobians of the dynamics along it, ONE launch, one dynamics pass per step (the factorisation of M inside the
+ * forward-dynamics-gradient pass gives qdd; its trajectory agrees with grid_rollout_*'s, which runs ABA, to rounding - not bit for bit).  Per solve and step:
+ *   qdd_t = FD(q_t, qd_t, u_t);  fx_t = [d qdd/dq | d qdd/dqd];  fu_t = d qdd/du = M^-1(q_t);  then the semi-implicit Euler update of grid_rollout_*
+ * x0, u, traj, xT and their strides exactly as grid_rollout_*, followed by
+ *   fx    (num_steps, num_solves, 2n^2): the df_du record of grid_forward_dynamics_gradient_* at (x_t, u_t), fx[col*n + row]; may be NULL
+ *   fu    (num_steps, num_solves, n^2): dense, exactly symmetric, fu[col*n + row]; may be NULL (the work that only M^-1 needs is then skipped)
+ * At least one of the four outputs must be given.  The discrete Jacobians of the step map x = [q; qd] follow without further dynamics (Fq | Fv = fx):
+ *   A_t = [[I + dt^2 Fq, dt (I + dt Fv)], [dt Fq, I + dt Fv]],  B_t = [[dt^2 fu], [dt fu]]
+ * num_steps == 0 copies x0 to traj / xT and writes no Jacobian.  Errors as grid_rollout_*. */
+/* no counterpart in the reference (launches rollout_linearized_kernel<T>): device buffers, asynchronous on `stream`, nothing allocated */
+int grid_rollout_linearized_device(grid_handle *h, const float *d_x0, int stride_x0, const float *d_u, long stride_u_step, int stride_u_solve, int num_solves, int num_steps,
+                                   float dt, float gravity, float *d_traj, float *d_xT, float *d_fx, float *d_fu, void *stream);
+/* no counterpart in the reference: host buffers, synchronous, stride_x0 in [2n, 3n], num_solves <= max_timesteps.  Everything is staged in device buffers of the
+ * handle that the first call allocates and longer calls grow; grid_close frees them.  Each staged output is capped at GRID_ROLLOUT_LIN_HOST_CAP_BYTES (1 GiB):
+ * a call whose fx (or fu, traj) record would be larger returns hipErrorInvalidValue with a grid_last_error text and leaves the handle usable - split the
+ * horizon (the final state of one call is the x0 of the next) or use the device entry point with buffers of your own. */
+#define GRID_ROLLOUT_LIN_HOST_CAP_BYTES ((size_t)1 << 30)
+int grid_rollout_linearized_host(grid_handle *h, const float *h_x0, int stride_x0, const float *h_u, long stride_u_step, int stride_u_solve, int num_solves, int num_steps,
+                                 float dt, float gravity, float *h_traj, float *h_xT, float *h_fx, float *h_fu);
+int grid_rollout_linearized_device_f64(grid_handle *h, const double *d_x0, int stride_x0, const double *d_u, long stride_u_step, int stride_u_solve, int num_solves,
+                                       int num_steps, double dt, double gravity, double *d_traj, double *d_xT, double *d_fx, double *d_fu, void *stream);
+int grid_rollout_linearized_host_f64(grid_handle *h, const double *h_x0, int stride_x0, const double *h_u, long stride_u_step, int stride_u_solve, int num_solves,
+                                     int num_steps, double dt, double gravity, double *h_traj, double *h_xT, double *h_fx, double *h_fu);
+
 /* in-kernel timing probe: replaces forward_dynamics_gradient_single_timing<T> (reference :236-248); returns microseconds per solve */
 int grid_forward_dynamics_gradient_single_timing(grid_handle *h, const float *h_q_qd_u, int reps, float gravity, float *h_df_du, double *us_per_call);
 
