@@ -68,6 +68,8 @@ TUNING_DEFAULTS = {
                                 # (algorithms/_branch_frame_gradient.py: branch_factor_by_branch)
     "fast_sincos": True,        # fp32 joint angles: branch-free Cody-Waite + minimax polynomials (29 instructions) instead of the math library's sincosf (120)
     "composite_scan": "f32",    # f32 | f64: precision of the suffix sums of the link inertias (tip/branch-frame paths); f64 = exact sums, rounded once
+    "adjoint_prefetch": "auto", # auto | True | False: rollout_adjoint_kernel requests g_t and the row of step t-1 before the dynamics of step t (five registers live across it) or
+                                # loads them after it; auto = before, except for 32-lane and wider lane groups (algorithms/_rollout_adjoint.py: gen_rollout_adjoint_prefetch)
     "base_origin": "auto",      # auto | off | <joint position>: tip-frame path - the joint-space inertia entries of the base half of a chain are
                                 # evaluated about the origin of this joint instead of the tip (fp32 accuracy); auto = L // 2 for L >= 5
 }
@@ -166,6 +168,10 @@ class GRiDCodeGenerator:
     from .algorithms import gen_rollout_linearized_layout, gen_rollout_linearized_constants, gen_rollout_linearized_device, gen_rollout_linearized_kernel, \
         gen_rollout_linearized_reserve, gen_rollout_linearized_host, gen_rollout_linearized
     from ._test import test_rollout_linearized
+    # rollout adjoint: gradients of a trajectory cost with respect to x0 and every u_t, one launch in reverse time (no counterpart in the reference)
+    from .algorithms import gen_rollout_adjoint_layout, gen_rollout_adjoint_constants, gen_rollout_adjoint_prefetch, gen_rollout_linearize_device, gen_rollout_adjoint_device, gen_rollout_adjoint_kernel, \
+        gen_rollout_adjoint_reserve, gen_rollout_adjoint_host, gen_rollout_adjoint
+    from ._test import test_rollout_adjoint
 
     def __init__(self, robotObj, DEBUG_MODE=False, NEED_PRINT_MAT=False, USE_DYNAMIC_SHARED_MEM=True, FILE_NAMESPACE="grid", COLS_PER_LANE=None, tuning=None):
         if not USE_DYNAMIC_SHARED_MEM:
@@ -401,6 +407,8 @@ class GRiDCodeGenerator:
                                  "    T *d_u_traj;", "    T *d_x_traj;", "    T *h_u_traj;", "    T *h_x_traj;",
                                  "    // LINEARISED ROLLOUT (reserved by rollout_linearized_reserve, not by init_gridData)",
                                  "    T *d_fx_traj;", "    T *d_fu_traj;", "    T *h_fx_traj;", "    T *h_fu_traj;",
+                                 "    // ROLLOUT ADJOINT (reserved by rollout_adjoint_reserve, not by init_gridData)",
+                                 "    T *d_gx_traj;", "    T *d_gu_traj;", "    T *d_gx0;", "    T *h_gx_traj;", "    T *h_gu_traj;", "    T *h_gx0;",
                                  "};"])
 
     def gen_init_gridData(self):
@@ -409,7 +417,8 @@ class GRiDCodeGenerator:
         host = [("h_q_qd_u", "3*NUM_JOINTS"), ("h_q_qd", "2*NUM_JOINTS"), ("h_q", "NUM_JOINTS"), ("h_c", "NUM_JOINTS"),
                 ("h_Minv", "NUM_JOINTS*NUM_JOINTS"), ("h_qdd", "NUM_JOINTS"), ("h_dc_du", "NUM_JOINTS*2*NUM_JOINTS"), ("h_df_du", "NUM_JOINTS*2*NUM_JOINTS")]
         unused = ["d_M", "d_eePos", "d_deePos", "d_d2eePos", "d_idsva_so", "d_df2", "h_M", "h_eePos", "h_deePos", "h_d2eePos", "h_idsva_so", "h_df2",
-                  "d_u_traj", "d_x_traj", "h_u_traj", "h_x_traj", "d_fx_traj", "d_fu_traj", "h_fx_traj", "h_fu_traj"]
+                  "d_u_traj", "d_x_traj", "h_u_traj", "h_x_traj", "d_fx_traj", "d_fu_traj", "h_fx_traj", "h_fu_traj",
+                  "d_gx_traj", "d_gu_traj", "d_gx0", "h_gx_traj", "h_gu_traj", "h_gx0"]
         if self.gen_idsva_so_available():
             dev += [("d_idsva_so", "4*NUM_JOINTS*NUM_JOINTS*NUM_JOINTS"), ("d_df2", "4*NUM_JOINTS*NUM_JOINTS*NUM_JOINTS")]
             host += [("h_idsva_so", "4*NUM_JOINTS*NUM_JOINTS*NUM_JOINTS"), ("h_df2", "4*NUM_JOINTS*NUM_JOINTS*NUM_JOINTS")]
@@ -475,6 +484,7 @@ class GRiDCodeGenerator:
                                  "grid_ee_release(&hd_data->d_M, &hd_data->h_M); // (allocated by the first crba host call)",
                                  "grid_ee_release(&hd_data->d_u_traj, &hd_data->h_u_traj); grid_ee_release(&hd_data->d_x_traj, &hd_data->h_x_traj); // (allocated by rollout_reserve)",
                                  "grid_ee_release(&hd_data->d_fx_traj, &hd_data->h_fx_traj); grid_ee_release(&hd_data->d_fu_traj, &hd_data->h_fu_traj); // (allocated by rollout_linearized_reserve)",
+                                 "grid_ee_release(&hd_data->d_gx_traj, &hd_data->h_gx_traj); grid_ee_release(&hd_data->d_gu_traj, &hd_data->h_gu_traj); grid_ee_release(&hd_data->d_gx0, &hd_data->h_gx0); // (allocated by rollout_adjoint_reserve)",
                                  "free(hd_data);",
                                  "for(int i=0; i<" + str(MAX_STREAMS) + "; i++){gpuErrchk(hipStreamDestroy(streams[i]));} free(streams);"])
         self.gen_add_end_function()
@@ -551,6 +561,7 @@ class GRiDCodeGenerator:
             self.gen_crba(use_thread_group)  # (outer namespace only, after the kinematics: its host wrappers reserve d_M / h_M with grid_ee_reserve)
             self.gen_rollout(use_thread_group)  # (outer namespace only; rollout_reserve uses grid_ee_reserve too)
             self.gen_rollout_linearized(use_thread_group)  # (after rollout: it calls grid_symplectic_euler_step and rollout_reserve)
+            self.gen_rollout_adjoint(use_thread_group)  # (after rollout_linearized: same slice, same inners, reverse time)
         if not self.nested:
             self.gen_init_close_grid()
 
@@ -629,6 +640,14 @@ class GRiDCodeGenerator:
                       "    __global__ rollout_linearized_kernel<T>(T *d_traj, T *d_xT, T *d_fx, T *d_fu, const T *d_x0, const int stride_x0, const T *d_u, const long stride_u_step, const int stride_u_solve, const robotModel<T> *d_robotModel, const T dt, const T gravity, const int NUM_TIMESTEPS, const int NUM_STEPS)",
                       "    __host__   rollout_linearized_reserve<T>(gridData<T> *hd_data, const int num_timesteps, const int num_steps)",
                       "    __host__   rollout_linearized<T>(gridData<T> *hd_data, const robotModel<T> *d_robotModel, const T dt, const T gravity, const int num_timesteps, const int num_steps, const dim3 block_dimms, const dim3 thread_dimms, hipStream_t *streams)",
+                      "",
+                      "    rollout adjoint, no counterpart in the reference: gradient of a trajectory cost with respect to x0 and every u_t from traj, u and gx = d cost / d traj (reverse time, no n^2 record leaves the chip):",
+                      "    __device__ rollout_linearize_device<T>(T *s_fx, const T *s_q, const T *s_qd, const T *s_tau, T *s_work, const robotModel<T> *d_robotModel, const T gravity, const int lane, const bool want_fu = true)",
+                      "    __device__ rollout_adjoint_contract_device<T>(T *s_gu, T *s_lam, T *s_w, const T *s_fx, const T *s_Minv, const T dt, const int lane, const T gq, const T gv, const bool want_gu = true)",
+                      "    __device__ rollout_adjoint_device<T>(T *s_gu, T *s_lam, T *s_w, T *s_fx, const T *s_q, const T *s_qd, const T *s_tau, T *s_work, const robotModel<T> *d_robotModel, const T dt, const T gravity, const int lane, const T gq, const T gv, const bool want_gu = true)",
+                      "    __global__ rollout_adjoint_kernel<T>(T *d_grad_x0, T *d_grad_u, const T *d_traj, const T *d_u, const long stride_u_step, const int stride_u_solve, const T *d_gx, const T *d_gxT, const robotModel<T> *d_robotModel, const T dt, const T gravity, const int NUM_TIMESTEPS, const int NUM_STEPS)",
+                      "    __host__   rollout_adjoint_reserve<T>(gridData<T> *hd_data, const int num_timesteps, const int num_steps)",
+                      "    __host__   rollout_adjoint<T>(gridData<T> *hd_data, const robotModel<T> *d_robotModel, const T dt, const T gravity, const int num_timesteps, const int num_steps, const dim3 block_dimms, const dim3 thread_dimms, hipStream_t *streams)",
                       "",
                       "Every host function also exists as NAME_single_timing and NAME_compute_only (no streams argument).",
                       "",

@@ -324,3 +324,25 @@ def test_rollout_linearized(self, q, qd, U, dt, GRAVITY=-9.81):
         Minv = test_minv(self, traj[t, :n], True)
         fu[t] = (0.5 * (Minv + Minv.T)).T.reshape(-1)
     return traj, fx, fu
+
+
+def test_rollout_adjoint(self, traj, U, dt, gx=None, gxT=None, GRAVITY=-9.81):
+    """(grad_x0 (2n), grad_u (T, n)): the gradient of L = sum_t <gx[t], x_t> (+ <gxT, x_T>) with respect to x0 and every u_t along the stored states traj (T+1, 2n)
+    of test_rollout under U (T, n): lam_T = gx[T] (+ gxT); for t = T-1 .. 0, with [Fq | Fv] = test_fd_grad and M^-1 = test_minv at (traj[t], U[t]),
+        w = lv + dt lq;  grad_u_t = dt M^-1 w;  lq <- gx[t, :n] + lq + dt Fq^T w;  lv <- gx[t, n:] + w + dt Fv^T w
+    what rollout_adjoint_kernel computes, in fp64."""
+    n = self.model.n
+    U = np.asarray(U, float).reshape(-1, n)
+    traj = np.asarray(traj, float).reshape(len(U) + 1, 2 * n)
+    g = np.zeros((len(U) + 1, 2 * n)) if gx is None else np.array(gx, float).reshape(len(U) + 1, 2 * n)
+    if gxT is not None:
+        g[-1] += np.asarray(gxT, float).reshape(2 * n)
+    lq, lv = g[-1, :n].copy(), g[-1, n:].copy()
+    grad_u = np.zeros((len(U), n))
+    for t in range(len(U) - 1, -1, -1):
+        F = test_fd_grad(self, traj[t, :n], traj[t, n:], U[t], GRAVITY)  # (n, 2n)
+        Minv = test_minv(self, traj[t, :n], True)
+        w = lv + dt * lq
+        grad_u[t] = dt * (0.5 * (Minv + Minv.T) @ w)
+        lq, lv = g[t, :n] + lq + dt * (F[:, :n].T @ w), g[t, n:] + w + dt * (F[:, n:].T @ w)
+    return np.concatenate([lq, lv]), grad_u

@@ -36,6 +36,7 @@ struct grid_typed {
     size_t M_cap = 0;  // elements of hd_data->d_M, the output staging of the crba host entry point (allocated by its first call; no pinned twin)
     size_t u_traj_cap = 0, x_traj_cap = 0;  // elements of hd_data->d_u_traj / d_x_traj, the staging of the rollout host entry point (same rules)
     size_t fx_traj_cap = 0, fu_traj_cap = 0;  // elements of hd_data->d_fx_traj / d_fu_traj, the Jacobian staging of the linearised rollout host entry point (same rules)
+    size_t gx_traj_cap = 0, gu_traj_cap = 0, gx0_cap = 0;  // elements of hd_data->d_gx_traj / d_gu_traj / d_gx0, the staging of the rollout adjoint host entry point (same rules)
 };
 
 // staging of the kinematics host entry points (grid_end_effector_pose*_host): allocated by the first kinematics call on a handle, never by grid_init,
@@ -860,6 +861,89 @@ static int rollout_linearized_host(grid_handle *h, const T *h_x0, int stride_x0,
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- rollout adjoint
+// The reverse pass over a stored trajectory: grad_x0 and grad_u of a cost whose gradient with respect to the states is gx (every step) and / or gxT (the final state).
+template <typename T>
+static int rollout_adjoint_check(const T *traj, const T *u, long stride_u_step, int stride_u_solve, int N, int num_steps, const T *gx, const T *gxT, const T *grad_x0, const T *grad_u) {
+    if (num_steps < 0) return fail_msg(hipErrorInvalidValue, "negative num_steps");
+    if (N == 0) return 0;
+    if (num_steps > 0 && (!traj || !u)) return fail_msg(hipErrorInvalidValue, "null input pointer: traj and u must be given");
+    if (!gx && !gxT) return fail_msg(hipErrorInvalidValue, "null cotangents: at least one of gx and gxT must be given");
+    if (!grad_x0 && !grad_u) return fail_msg(hipErrorInvalidValue, "null output pointers: at least one of grad_x0 and grad_u must be given");
+    const int n = (int)grid::NUM_JOINTS;
+    if ((long)N * 2 * n > (long)INT_MAX) return fail_msg(hipErrorInvalidValue, "2n * num_solves exceeds the 32-bit offsets the kernel uses inside one step");
+    return check_rollout_strides(2 * n, stride_u_step, stride_u_solve, N, num_steps);
+}
+
+template <typename T>
+static int rollout_adjoint_device(grid_handle *h, const T *d_traj, const T *d_u, long stride_u_step, int stride_u_solve, int N, int num_steps, T dt, T gravity,
+                                  const T *d_gx, const T *d_gxT, T *d_grad_x0, T *d_grad_u, void *stream) {
+    int rc = check_args(h, N);
+    if (rc) return rc;
+    if ((rc = rollout_adjoint_check<T>(d_traj, d_u, stride_u_step, stride_u_solve, N, num_steps, d_gx, d_gxT, d_grad_x0, d_grad_u))) return rc;
+    if (N == 0) return 0;
+    if (num_steps == 0 && !d_grad_x0) return 0;  // (no step: no grad_u is written)
+    GRID_ON_DEVICE(h);
+    if ((rc = ensure_typed<T>(h))) return rc;
+    launch_cfg c;
+    if ((rc = make_launch<T>(h, N, grid::ROLLOUT_ADJ_SUGGESTED_THREADS, grid::GRID_MAX_SOLVES_PER_BLOCK, grid::ROLLOUT_ADJ_LDS_PER_SOLVE, grid::ROLLOUT_ADJ_OUT_PER_SOLVE, &c))) return rc;
+    hipLaunchKernelGGL((grid::rollout_adjoint_kernel<T>), c.grid, c.block, c.lds, (hipStream_t)stream, d_grad_x0, num_steps > 0 ? d_grad_u : static_cast<T *>(nullptr), d_traj, d_u,
+                       stride_u_step, stride_u_solve, d_gx, d_gxT, typed<T>(h).d_robotModel, dt, gravity, N, num_steps);
+    GRID_TRY(hipGetLastError());
+    return 0;
+}
+
+// Host buffers in, host buffers out, synchronous.  traj and u pass through the handle's d_x_traj / d_u_traj like rollout_host, gx, gxT and the two gradients through
+// hd_data->d_gx_traj / d_gx0 / d_gu_traj (null after init_gridData, allocated here on first use, grown by longer calls, freed by close_grid; gxT rides behind gx).
+// No staged record may exceed GRID_ROLLOUT_LIN_HOST_CAP_BYTES: such a call is refused before anything is allocated or copied.
+template <typename T>
+static int rollout_adjoint_host(grid_handle *h, const T *h_traj, const T *h_u, long stride_u_step, int stride_u_solve, int N, int num_steps, T dt, T gravity,
+                                const T *h_gx, const T *h_gxT, T *h_grad_x0, T *h_grad_u) {
+    int rc = host_prologue<T>(h, N);
+    if (rc) return rc;
+    if ((rc = rollout_adjoint_check<T>(h_traj, h_u, stride_u_step, stride_u_solve, N, num_steps, h_gx, h_gxT, h_grad_x0, h_grad_u))) return rc;
+    if (N == 0) return 0;
+    const size_t n = grid::NUM_JOINTS;
+    const size_t u_span = stride_u_solve == 0 ? n : (size_t)(N - 1) * stride_u_solve + n;
+    const size_t u_count = num_steps > 0 ? (size_t)(num_steps - 1) * (size_t)stride_u_step + u_span : 0;
+    const size_t row = 2 * n * (size_t)N;
+    const size_t x_count = row * ((size_t)num_steps + 1);
+    const size_t gx_count = (h_gx ? x_count : 0) + (h_gxT ? row : 0);
+    const size_t gu_count = h_grad_u ? n * (size_t)N * (size_t)num_steps : 0;
+    const size_t cap = GRID_ROLLOUT_LIN_HOST_CAP_BYTES / sizeof(T);
+    if (x_count > cap || gx_count > cap || u_count > cap) {
+        snprintf(g_err, sizeof(g_err), "rollout_adjoint host staging capacity exceeded: %d solves x %d steps need %zu bytes for the largest record, the cap is %zu "
+                 "(split the horizon or use the device entry point)", N, num_steps,
+                 (gx_count > x_count ? (gx_count > u_count ? gx_count : u_count) : (x_count > u_count ? x_count : u_count)) * sizeof(T), (size_t)GRID_ROLLOUT_LIN_HOST_CAP_BYTES);
+        return (int)hipErrorInvalidValue;
+    }
+    if (num_steps == 0 && !h_grad_x0) return 0;
+    GRID_ON_DEVICE(h);
+    if ((rc = ensure_typed<T>(h))) return rc;
+    grid::gridData<T> *d = typed<T>(h).hd_data;
+    {
+        std::lock_guard<std::mutex> lock(h->alloc_lock);
+        if ((rc = ee_grow<T>(&d->d_u_traj, &typed<T>(h).u_traj_cap, u_count > 0 ? u_count : 1))) return rc;
+        if ((rc = ee_grow<T>(&d->d_x_traj, &typed<T>(h).x_traj_cap, x_count))) return rc;
+        if ((rc = ee_grow<T>(&d->d_gx_traj, &typed<T>(h).gx_traj_cap, gx_count))) return rc;
+        if (gu_count > 0 && (rc = ee_grow<T>(&d->d_gu_traj, &typed<T>(h).gu_traj_cap, gu_count))) return rc;
+        if (h_grad_x0 && (rc = ee_grow<T>(&d->d_gx0, &typed<T>(h).gx0_cap, row))) return rc;
+    }
+    const T *d_gx = h_gx ? d->d_gx_traj : nullptr;
+    const T *d_gxT = h_gxT ? d->d_gx_traj + (h_gx ? x_count : 0) : nullptr;
+    T *d_grad_x0 = h_grad_x0 ? d->d_gx0 : nullptr, *d_grad_u = gu_count > 0 ? d->d_gu_traj : nullptr;
+    hipStream_t s = h->streams[0];
+    if (num_steps > 0) GRID_H2D(d->d_x_traj, h_traj, row * (size_t)num_steps);  // (row num_steps of traj is not read)
+    if (u_count > 0) GRID_H2D(d->d_u_traj, h_u, u_count);
+    if (h_gx) GRID_H2D(d->d_gx_traj, h_gx, x_count);
+    if (h_gxT) GRID_H2D(d->d_gx_traj + (h_gx ? x_count : 0), h_gxT, row);
+    if ((rc = rollout_adjoint_device<T>(h, d->d_x_traj, d->d_u_traj, stride_u_step, stride_u_solve, N, num_steps, dt, gravity, d_gx, d_gxT, d_grad_x0, d_grad_u, (void *)s))) return rc;
+    if (d_grad_x0) GRID_D2H(h_grad_x0, d_grad_x0, row);
+    if (d_grad_u) GRID_D2H(h_grad_u, d_grad_u, gu_count);
+    GRID_TRY(hipStreamSynchronize(s));
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- multi-GPU driver
 // One process, G handles (one per GPU): the batch [0, N) is cut into G contiguous ranges of ceil(N/G) solves (SURVEY.md section 8(e),
 // 16 384 total -> 16 384/G per GPU, no collective).  Every device has its own robotModel copy and stream.
@@ -1191,6 +1275,22 @@ int grid_rollout_linearized_device_f64(grid_handle *h, const double *d_x0, int s
 int grid_rollout_linearized_host_f64(grid_handle *h, const double *h_x0, int stride_x0, const double *h_u, long stride_u_step, int stride_u_solve, int num_solves,
                                      int num_steps, double dt, double gravity, double *h_traj, double *h_xT, double *h_fx, double *h_fu) {
     GRID_GUARDED(return rollout_linearized_host<double>(h, h_x0, stride_x0, h_u, stride_u_step, stride_u_solve, num_solves, num_steps, dt, gravity, h_traj, h_xT, h_fx, h_fu);)
+}
+int grid_rollout_adjoint_device(grid_handle *h, const float *d_traj, const float *d_u, long stride_u_step, int stride_u_solve, int num_solves, int num_steps, float dt, float gravity,
+                                const float *d_gx, const float *d_gxT, float *d_grad_x0, float *d_grad_u, void *stream) {
+    GRID_GUARDED(return rollout_adjoint_device<float>(h, d_traj, d_u, stride_u_step, stride_u_solve, num_solves, num_steps, dt, gravity, d_gx, d_gxT, d_grad_x0, d_grad_u, stream);)
+}
+int grid_rollout_adjoint_host(grid_handle *h, const float *h_traj, const float *h_u, long stride_u_step, int stride_u_solve, int num_solves, int num_steps, float dt, float gravity,
+                              const float *h_gx, const float *h_gxT, float *h_grad_x0, float *h_grad_u) {
+    GRID_GUARDED(return rollout_adjoint_host<float>(h, h_traj, h_u, stride_u_step, stride_u_solve, num_solves, num_steps, dt, gravity, h_gx, h_gxT, h_grad_x0, h_grad_u);)
+}
+int grid_rollout_adjoint_device_f64(grid_handle *h, const double *d_traj, const double *d_u, long stride_u_step, int stride_u_solve, int num_solves, int num_steps, double dt,
+                                    double gravity, const double *d_gx, const double *d_gxT, double *d_grad_x0, double *d_grad_u, void *stream) {
+    GRID_GUARDED(return rollout_adjoint_device<double>(h, d_traj, d_u, stride_u_step, stride_u_solve, num_solves, num_steps, dt, gravity, d_gx, d_gxT, d_grad_x0, d_grad_u, stream);)
+}
+int grid_rollout_adjoint_host_f64(grid_handle *h, const double *h_traj, const double *h_u, long stride_u_step, int stride_u_solve, int num_solves, int num_steps, double dt,
+                                  double gravity, const double *h_gx, const double *h_gxT, double *h_grad_x0, double *h_grad_u) {
+    GRID_GUARDED(return rollout_adjoint_host<double>(h, h_traj, h_u, stride_u_step, stride_u_solve, num_solves, num_steps, dt, gravity, h_gx, h_gxT, h_grad_x0, h_grad_u);)
 }
 
 int grid_forward_dynamics_gradient_single_timing(grid_handle *h, const float *h_q_qd_u, int reps, float gravity, float *h_df_du, double *us_per_call) {

@@ -318,6 +318,48 @@ class GridLibrary:
     def rollout_linearized_host_f64(self, x0, u, dt, gravity=9.81, want=("traj", "fx", "fu")):
         return self._rollout_linearized_host(x0, u, dt, gravity, np.float64, tuple(want))
 
+    # ---- rollout adjoint: gradient of a trajectory cost with respect to x0 and every u_t from the stored states, the controls and gx = d cost / d traj
+    def _rollout_adjoint_host(self, traj, u, dt, gx, gxT, gravity, dtype, want):
+        n = self.n
+        tr = np.ascontiguousarray(traj, dtype=dtype)
+        if tr.ndim != 3 or tr.shape[2] != 2 * n:
+            raise ValueError("traj must have shape (T+1, N, 2n) with n = %d" % n)
+        T, N = tr.shape[0] - 1, tr.shape[1]
+        uu = np.ascontiguousarray(u, dtype=dtype)
+        if uu.ndim == 2 and uu.shape == (T, n):
+            stride_solve, stride_step = 0, n
+        elif uu.ndim == 3 and uu.shape == (T, N, n):
+            stride_solve, stride_step = n, N * n
+        else:
+            raise ValueError("u must have shape (T, N, n) or (T, n) with T = %d, N = %d, n = %d" % (T, N, n))
+        want = tuple(want)
+        if not want or any(k not in ("grad_x0", "grad_u") for k in want):
+            raise ValueError('want must name "grad_x0" and / or "grad_u"')
+        g = None if gx is None else np.ascontiguousarray(gx, dtype=dtype)
+        gT = None if gxT is None else np.ascontiguousarray(gxT, dtype=dtype)
+        if g is not None and g.shape != tr.shape:
+            raise ValueError("gx must have the shape of traj")
+        if gT is not None and gT.shape != (N, 2 * n):
+            raise ValueError("gxT must have shape (N, 2n)")
+        shapes = {"grad_x0": (N, 2 * n), "grad_u": (T, N, n)}
+        out = {k: np.empty(shapes[k], dtype=dtype) for k in want}
+        P = lambda a: ctypes.c_void_p(a.ctypes.data if a is not None and a.size else None)
+        real = ctypes.c_double if dtype == np.float64 else ctypes.c_float
+        fn = self.lib.grid_rollout_adjoint_host_f64 if dtype == np.float64 else self.lib.grid_rollout_adjoint_host
+        self._check(fn(self.handle, P(tr), P(uu), ctypes.c_long(stride_step), ctypes.c_int(stride_solve), ctypes.c_int(N), ctypes.c_int(T), real(dt), real(gravity),
+                       P(g), P(gT), P(out.get("grad_x0")), P(out.get("grad_u"))))
+        return tuple(out[k] for k in want)
+
+    def rollout_adjoint_host(self, traj, u, dt, gx=None, gxT=None, gravity=9.81, want=("grad_x0", "grad_u")):
+        """The reverse pass of rollout in one launch -> (grad_x0 (N, 2n), grad_u (T, N, n)) in float32: the gradient of a cost L = sum_t l_t(x_t) with respect to
+        x0 and every u_t.  traj (T+1, N, 2n) and u ((T, N, n), or (T, n) shared) are what rollout_host read and wrote; gx (T+1, N, 2n) = d L / d traj and / or
+        gxT (N, 2n) = d L / d x_T (at least one; both add at step T).  want: which of "grad_x0", "grad_u" to compute and return, in that order (without "grad_u"
+        the work only M^-1 needs is skipped).  grad_u is ALWAYS per solve: for a shared u the gradient with respect to the one sequence is grad_u.sum(axis=1)."""
+        return self._rollout_adjoint_host(traj, u, dt, gx, gxT, gravity, np.float32, want)
+
+    def rollout_adjoint_host_f64(self, traj, u, dt, gx=None, gxT=None, gravity=9.81, want=("grad_x0", "grad_u")):
+        return self._rollout_adjoint_host(traj, u, dt, gx, gxT, gravity, np.float64, want)
+
     def forward_dynamics_host(self, q_qd_u, gravity=9.81, aba=False):
         x = self._host_in(q_qd_u, 3 * self.n, "q_qd_u")
         out = np.empty((x.shape[0], self.n), dtype=np.float32)
@@ -451,6 +493,28 @@ class GridLibrary:
                                                             ctypes.c_int(0 if u_shared else n), ctypes.c_int(N), ctypes.c_int(T), ctypes.c_float(dt), ctypes.c_float(gravity),
                                                             _ptr(d_traj), _ptr(d_xT), _ptr(d_fx), _ptr(d_fu), ctypes.c_void_p(stream)))
 
+    def _rollout_adjoint_device(self, fn, real, d_traj, d_u, N, T, dt, d_gx, d_gxT, d_grad_x0, d_grad_u, u_shared, gravity, stream):
+        n = self.n
+        self._check(fn(self.handle, _ptr(d_traj), _ptr(d_u), ctypes.c_long(n if u_shared else N * n), ctypes.c_int(0 if u_shared else n), ctypes.c_int(N), ctypes.c_int(T),
+                       real(dt), real(gravity), _ptr(d_gx), _ptr(d_gxT), _ptr(d_grad_x0), _ptr(d_grad_u), ctypes.c_void_p(stream)))
+
+    def rollout_adjoint_device(self, d_traj, d_u, N, T, dt, d_gx=None, d_gxT=None, d_grad_x0=None, d_grad_u=None, u_shared=False, gravity=9.81, stream=0):
+        """Asynchronous on `stream`, allocates nothing.  d_traj (T+1, N, 2n) and d_u (dense (T, N, n), or with u_shared ONE sequence (T, n)) as rollout_device read
+        and wrote them; cotangents d_gx (T+1, N, 2n) and / or d_gxT (N, 2n): at least one; outputs d_grad_x0 (N, 2n) and / or d_grad_u (T, N, n): at least one
+        (torch tensors or raw addresses, float32).  d_grad_u is ALWAYS per solve: with u_shared the gradient of the one sequence is its sum over the solves."""
+        self._rollout_adjoint_device(self.lib.grid_rollout_adjoint_device, ctypes.c_float, d_traj, d_u, N, T, dt, d_gx, d_gxT, d_grad_x0, d_grad_u, u_shared, gravity, stream)
+
+    def rollout_adjoint_device_f64(self, d_traj, d_u, N, T, dt, d_gx=None, d_gxT=None, d_grad_x0=None, d_grad_u=None, u_shared=False, gravity=9.81, stream=0):
+        self._rollout_adjoint_device(self.lib.grid_rollout_adjoint_device_f64, ctypes.c_double, d_traj, d_u, N, T, dt, d_gx, d_gxT, d_grad_x0, d_grad_u, u_shared, gravity, stream)
+
+    def rollout_torch(self, x0, u, dt, gravity=9.81):
+        """Differentiable rollout on torch tensors: traj (T+1, N, 2n) = rollout(x0, u) with autograd support.  x0 (N, 2n); u (T, N, n), or (T, n) shared by all
+        solves (its gradient is the sum of the per-solve gradients over N); float32 or float64, x0 and u on the same device.  CUDA tensors go through the device
+        entry points on torch's current stream (no host synchronisation; the outputs are the only allocations), CPU tensors through the host entry points.
+        Forward is rollout (ABA), backward is rollout_adjoint on the saved traj and u; only the gradients autograd asks for are computed.  First order only:
+        differentiating the backward pass raises."""
+        return _rollout_function()(self, float(dt), float(gravity), x0, u)
+
     def forward_dynamics_device(self, d_q_qd_u, N, d_qdd, stride=None, gravity=9.81, stream=0):
         self._check(self.lib.grid_forward_dynamics_device(self.handle, _ptr(d_q_qd_u), ctypes.c_int(stride or 3 * self.n), ctypes.c_int(N),
                                                           ctypes.c_float(gravity), _ptr(d_qdd), ctypes.c_void_p(stream)))
@@ -529,6 +593,91 @@ def discrete_jacobians(fx, fu, dt):
     A = cat([cat([top_q, top_v], -1), cat([low_q, low_v], -1)], -2)
     B = cat([(dt * dt) * M, dt * M], -2)
     return A, B
+
+
+_ROLLOUT_FUNCTION = None
+
+
+def _rollout_function():
+    """The torch.autograd.Function behind GridLibrary.rollout_torch (built on first use: importing this module does not import torch)."""
+    global _ROLLOUT_FUNCTION
+    if _ROLLOUT_FUNCTION is not None:
+        return _ROLLOUT_FUNCTION
+    import torch
+
+    def _real(t):
+        return ctypes.c_double if t.dtype == torch.float64 else ctypes.c_float
+
+    def _stream(t):
+        return torch.cuda.current_stream(t.device).cuda_stream
+
+    class _RolloutAdjoint(torch.autograd.Function):
+        """grad_x0, grad_u = adjoint(traj, u, g): a Function of its own so that a second differentiation meets a backward that says what is missing."""
+
+        @staticmethod
+        def forward(ctx, lib, dt, gravity, traj, u, g, want_x0, want_u):
+            n, (T1, N) = lib.n, traj.shape[:2]
+            T, shared = T1 - 1, u.dim() == 2
+            g = g.detach().contiguous()
+            gx0 = torch.empty((N, 2 * n), dtype=traj.dtype, device=traj.device) if want_x0 else None
+            gu = torch.empty((T, N, n), dtype=traj.dtype, device=traj.device) if (want_u and T > 0) else None
+            if gx0 is None and gu is None:
+                return None, (torch.zeros_like(u) if want_u else None)
+            if traj.is_cuda:
+                fn = lib.lib.grid_rollout_adjoint_device_f64 if traj.dtype == torch.float64 else lib.lib.grid_rollout_adjoint_device
+                with torch.cuda.device(traj.device):
+                    lib._rollout_adjoint_device(fn, _real(traj), traj, u, N, T, dt, g, None, gx0, gu, shared, gravity, _stream(traj))
+            else:
+                f = lib.rollout_adjoint_host_f64 if traj.dtype == torch.float64 else lib.rollout_adjoint_host
+                res = f(traj.numpy(), u.numpy(), dt, gx=g.numpy(), gravity=gravity, want=tuple(k for k, w in (("grad_x0", gx0 is not None), ("grad_u", gu is not None)) if w))
+                for dst, src in zip([o for o in (gx0, gu) if o is not None], res):
+                    dst.copy_(torch.from_numpy(src))
+            if want_u and gu is None:
+                gu = torch.empty((0,) + tuple(u.shape[1:]), dtype=u.dtype, device=u.device)
+            elif gu is not None and shared:
+                gu = gu.sum(dim=1)
+            return gx0, gu
+
+        @staticmethod
+        def backward(ctx, *grads):
+            raise RuntimeError("rollout_torch is differentiable once: the second-order terms of the rollout (double backward) are not implemented")
+
+    class _Rollout(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, lib, dt, gravity, x0, u):
+            n = lib.n
+            if x0.dtype not in (torch.float32, torch.float64) or u.dtype != x0.dtype or u.device != x0.device:
+                raise TypeError("x0 and u must be float32 or float64 tensors of one dtype on one device")
+            if x0.dim() != 2 or x0.shape[1] != 2 * n:
+                raise ValueError("x0 must have shape (N, 2n) with n = %d" % n)
+            N = x0.shape[0]
+            if not ((u.dim() == 2 and u.shape[1] == n) or (u.dim() == 3 and tuple(u.shape[1:]) == (N, n))):
+                raise ValueError("u must have shape (T, N, n) or (T, n) with N = %d, n = %d" % (N, n))
+            x0c, uc = x0.detach().contiguous(), u.detach().contiguous()
+            T, shared = uc.shape[0], uc.dim() == 2
+            traj = torch.empty((T + 1, N, 2 * n), dtype=x0.dtype, device=x0.device)
+            if x0.is_cuda:
+                fn = lib.lib.grid_rollout_device_f64 if x0.dtype == torch.float64 else lib.lib.grid_rollout_device
+                real = _real(x0)
+                with torch.cuda.device(x0.device):
+                    lib._check(fn(lib.handle, _ptr(x0c), ctypes.c_int(2 * n), _ptr(uc), ctypes.c_long(n if shared else N * n), ctypes.c_int(0 if shared else n), ctypes.c_int(N),
+                                  ctypes.c_int(T), real(dt), real(gravity), _ptr(traj), _ptr(None), ctypes.c_void_p(_stream(x0))))
+            else:
+                f = lib.rollout_host_f64 if x0.dtype == torch.float64 else lib.rollout_host
+                traj.copy_(torch.from_numpy(f(x0c.numpy(), uc.numpy(), dt, gravity=gravity)))
+            ctx.lib, ctx.dt, ctx.gravity = lib, dt, gravity
+            ctx.save_for_backward(traj, uc)
+            return traj
+
+        @staticmethod
+        def backward(ctx, g):
+            traj, uc = ctx.saved_tensors
+            want_x0, want_u = ctx.needs_input_grad[3], ctx.needs_input_grad[4]
+            gx0, gu = _RolloutAdjoint.apply(ctx.lib, ctx.dt, ctx.gravity, traj, uc, g, want_x0, want_u)
+            return None, None, None, gx0, gu
+
+    _ROLLOUT_FUNCTION = _Rollout.apply
+    return _ROLLOUT_FUNCTION
 
 
 def load(robot_name, device=0, max_timesteps=16384, build_dir=None):

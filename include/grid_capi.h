@@ -229,6 +229,33 @@ int grid_rollout_linearized_device_f64(grid_handle *h, const double *d_x0, int s
 int grid_rollout_linearized_host_f64(grid_handle *h, const double *h_x0, int stride_x0, const double *h_u, long stride_u_step, int stride_u_solve, int num_solves,
                                      int num_steps, double dt, double gravity, double *h_traj, double *h_xT, double *h_fx, double *h_fu);
 
+/* Rollout adjoint: the gradient of a scalar cost of a trajectory, L = sum_t l_t(x_t), with respect to x0 and every u_t, ONE launch in reverse time.  The caller has
+ * rolled out (grid_rollout_* or grid_rollout_linearized_*) and hands back what that call read and wrote, together with g_t = d l_t / d x_t.  Per solve, with the discrete
+ * Jacobians A_t, B_t of grid_rollout_linearized_*:
+ *   lam_T = g_T;   t = T-1 .. 0:  grad_u_t = B_t^T lam_{t+1},  lam_t = g_t + A_t^T lam_{t+1};   grad_x0 = lam_0
+ * Every step is re-linearised on chip at (traj[t], u[t]) and contracted with lam on the spot: no n^2-sized record is written.  Cost terms in u are the caller's own.
+ *   traj    (num_steps+1, num_solves, 2n): the states the rollout wrote for u (row num_steps is not read; with num_steps == 0 neither traj nor u is)
+ *   u       element (t, k, j) at u[t*stride_u_step + k*stride_u_solve + j]; strides as grid_rollout_*; stride_u_solve == 0: one sequence for all solves
+ *   gx      (num_steps+1, num_solves, 2n): d cost / d traj; may be NULL
+ *   gxT     (num_solves, 2n): d cost / d x_T; may be NULL; at least one of gx, gxT; where both are given gxT is added to row num_steps of gx
+ *   grad_x0 (num_solves, 2n); may be NULL
+ *   grad_u  (num_steps, num_solves, n): always per solve - for a shared control sequence the caller sums over the solves; may be NULL (the work only M^-1 needs
+ *           is then skipped); at least one of grad_x0, grad_u
+ * num_steps == 0 gives grad_x0 = gx[0] (+ gxT) and writes no grad_u.  Errors (return code != 0, text in grid_last_error, handle stays usable): negative counts, NULL traj or
+ * u with num_steps > 0, both cotangents NULL, both outputs NULL, a solve stride that is neither 0 nor >= n, a step stride shorter than one step spans. */
+/* no counterpart in the reference (launches rollout_adjoint_kernel<T>): device buffers, asynchronous on `stream`, nothing allocated */
+int grid_rollout_adjoint_device(grid_handle *h, const float *d_traj, const float *d_u, long stride_u_step, int stride_u_solve, int num_solves, int num_steps, float dt, float gravity,
+                                const float *d_gx, const float *d_gxT, float *d_grad_x0, float *d_grad_u, void *stream);
+/* no counterpart in the reference: host buffers, synchronous, num_solves <= max_timesteps.  Everything is staged in device buffers of the handle that the first call
+ * allocates and longer calls grow; grid_close frees them.  Each staged record is capped at GRID_ROLLOUT_LIN_HOST_CAP_BYTES (1 GiB): a longer call returns
+ * hipErrorInvalidValue with a grid_last_error text before anything is allocated and leaves the handle usable - use the device entry point with buffers of your own. */
+int grid_rollout_adjoint_host(grid_handle *h, const float *h_traj, const float *h_u, long stride_u_step, int stride_u_solve, int num_solves, int num_steps, float dt, float gravity,
+                              const float *h_gx, const float *h_gxT, float *h_grad_x0, float *h_grad_u);
+int grid_rollout_adjoint_device_f64(grid_handle *h, const double *d_traj, const double *d_u, long stride_u_step, int stride_u_solve, int num_solves, int num_steps, double dt,
+                                    double gravity, const double *d_gx, const double *d_gxT, double *d_grad_x0, double *d_grad_u, void *stream);
+int grid_rollout_adjoint_host_f64(grid_handle *h, const double *h_traj, const double *h_u, long stride_u_step, int stride_u_solve, int num_solves, int num_steps, double dt,
+                                  double gravity, const double *h_gx, const double *h_gxT, double *h_grad_x0, double *h_grad_u);
+
 /* in-kernel timing probe: replaces forward_dynamics_gradient_single_timing<T> (reference :236-248); returns microseconds per solve */
 int grid_forward_dynamics_gradient_single_timing(grid_handle *h, const float *h_q_qd_u, int reps, float gravity, float *h_df_du, double *us_per_call);
 
