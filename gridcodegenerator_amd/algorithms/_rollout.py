@@ -20,6 +20,8 @@ The lane groups of a wave own consecutive solves, so row t of a wave is written 
 
 LDS: the slice of aba_kernel as it is: q | qd | u sit in GRID_OFF_IN and qdd goes into its spare fourth slot; the staging record is [q | qd].
 """
+from ._rollout_common import gen_rollout_commit_control, gen_rollout_family_host, gen_rollout_family_reserve, gen_rollout_kernel_head, gen_rollout_load_x0, \
+    gen_rollout_prefetch_control, gen_rollout_save, gen_rollout_step_loop
 
 
 def gen_rollout_constants(self):
@@ -68,28 +70,6 @@ def gen_rollout_device(self, use_thread_group=False):
     self.gen_add_end_function()
 
 
-def _gen_rollout_save_row(self, row_ptr_expr, name, single_call_timing, use_thread_group):
-    """Stages [q | qd] of this solve and stores the wave's rows to `row_ptr_expr` (a T* to row 0 of the time slice)."""
-    n = self.model.n
-    if not single_call_timing:
-        # the saver's addresses and counts depend on tid, grp and k alone: invariants that LLVM hoists out of the step loop (and out of the batch loop) and
-        # keeps in VGPRs across the ABA (chain12, 245 VGPRs in aba_kernel, then spills).  Opaque copies make it rebuild them per row: a handful of integer instructions.
-        self.gen_add_code_line("const int tid_t = grid_loop_variant(tid); const int grp_t = grid_loop_variant(grp); const int k_t = grid_loop_variant(k);")
-        self.gen_add_code_line("{ const int tid = tid_t; const int grp = grp_t; const int k = k_t; (void)tid; // (shadow the invariants)", True)
-    else:
-        self.gen_add_code_line("{", True)
-    self.gen_add_code_line("T *d_%s = %s;" % (name, row_ptr_expr))
-    self.gen_add_parallel_loop("ind", str(2 * n), use_thread_group)
-    self.gen_add_code_line("s_out[ind] = s_x[ind];")
-    self.gen_add_end_control_flow()
-    if single_call_timing:
-        self.gen_kernel_save_result_single_timing(name, 2 * n, use_thread_group, "s_out")
-        self.gen_add_sync(use_thread_group)
-    else:
-        self.gen_kernel_save_result(name, 2 * n, 2 * n, use_thread_group, "s_out")
-    self.gen_add_end_control_flow()
-
-
 def gen_rollout_kernel(self, use_thread_group=False, single_call_timing=False):
     n = self.model.n
     func_params = ["d_traj is the state trajectory (NUM_STEPS+1, NUM_TIMESTEPS, 2n), row 0 is x0, or nullptr: nothing is written during the loop",
@@ -118,94 +98,54 @@ def gen_rollout_kernel(self, use_thread_group=False, single_call_timing=False):
     self.gen_kernel_prologue("ROLLOUT_LDS_PER_SOLVE")
     self.gen_add_code_lines(["T *s_x = &s_mem[GRID_OFF_IN]; T *s_x0 = s_x; T *s_q = s_x; T *s_qd = &s_x[%d]; T *s_tau = &s_x[%d]; T *s_qdd = &s_mem[ROLLOUT_OFF_QDD];" % (n, 2 * n),
                              "T *s_out = &s_out_all[grp*%d];" % (2 * n)])
-    if single_call_timing:
-        self.gen_add_code_line("const int k = 0; const int kc = 0; const bool valid = (blockIdx.x + blockIdx.y == 0) && (grp == 0); const int lane = lane_id; const size_t row_stride = %d; (void)k; (void)NUM_TIMESTEPS;" % (2 * n))
-        self.gen_add_code_line("if (!valid) {return;}")
-    else:
-        self.gen_add_parallel_loop("k", "NUM_TIMESTEPS", use_thread_group, block_level=True)
-        self.gen_add_code_line("const size_t row_stride = static_cast<size_t>(NUM_TIMESTEPS)*%d; // elements between two time slices of d_traj" % (2 * n))
-    self.gen_add_code_line("T r_u = (NUM_STEPS > 0 && lane < %d) ? d_u[kc*stride_u_solve + lane] : static_cast<T>(0); // control of step 0, in flight while x0 arrives" % n)
-    self.gen_kernel_load_inputs("x0", "stride_x0", 2 * n, use_thread_group)
-    self.gen_add_code_line("if (lane < %d) { s_tau[lane] = r_u; }" % n)
-    self.gen_add_sync(use_thread_group)
+    gen_rollout_kernel_head(self, [("row", 2 * n)], "d_traj", single_call_timing, use_thread_group)
+    gen_rollout_load_x0(self, use_thread_group)
+    save_row = lambda row_ptr_expr, name: gen_rollout_save(self, row_ptr_expr, name, 2 * n, "s_out", single_call_timing, use_thread_group, "s_x")
     self.gen_add_code_line("if (d_traj != nullptr) { // row 0 is x0", True)
-    _gen_rollout_save_row(self, "d_traj", "traj_t", single_call_timing, use_thread_group)
+    save_row("d_traj", "traj_t")
     self.gen_add_end_control_flow()
-    self.gen_add_code_line("for (int t = 0; t < NUM_STEPS; t++){", True)
-    self.gen_add_code_line("const int lane = grid_loop_variant(lane_id); // (shadows the outer one: keeps lane-dependent values from being hoisted out of the step loop and spilled)")
+    gen_rollout_step_loop(self)
     self.gen_add_code_line("// the next step's control leaves for the registers now and lands in LDS after this step")
     self.gen_add_code_line("// (wave-uniform 64-bit step base + 32-bit lane offset, rebuilt from k every step: no pointer is kept alive across the ABA)")
-    self.gen_add_code_line("const T *d_u_t = d_u + static_cast<long>(t + 1)*stride_u_step;")
-    self.gen_add_code_line("r_u = (t + 1 < NUM_STEPS && lane < %d) ? d_u_t[%s*stride_u_solve + lane] : static_cast<T>(0);" % (n, "kc" if single_call_timing else "(k < NUM_TIMESTEPS ? k : NUM_TIMESTEPS - 1)"))
+    gen_rollout_prefetch_control(self, single_call_timing)
     self.gen_add_code_line("rollout_device<T>(s_q, s_qd, s_tau, s_qdd, s_mem, d_robotModel, dt, gravity, lane);")
-    self.gen_add_code_line("if (lane < %d) { s_tau[lane] = r_u; }" % n)
-    self.gen_add_sync(use_thread_group)
+    gen_rollout_commit_control(self, use_thread_group)
     self.gen_add_code_line("if (d_traj != nullptr) {", True)
-    _gen_rollout_save_row(self, "d_traj + static_cast<size_t>(t + 1)*row_stride", "traj_t", single_call_timing, use_thread_group)
+    save_row("d_traj + static_cast<size_t>(t + 1)*row_stride", "traj_t")
     self.gen_add_end_control_flow()
     self.gen_add_end_control_flow()
     self.gen_add_code_line("if (d_xT != nullptr) {", True)
-    _gen_rollout_save_row(self, "d_xT", "xT_k", single_call_timing, use_thread_group)
+    save_row("d_xT", "xT_k")
     self.gen_add_end_control_flow()
     if not single_call_timing:
         self.gen_add_end_control_flow()
     self.gen_add_end_function()
 
 
+ROLLOUT_RESERVE = dict(
+    name="rollout", base=None, min_steps=0,
+    doc=("Reserves the rollout buffers of hd_data for num_timesteps solves of num_steps steps (the reference's gridData has no such buffers)",
+         ["d_u_traj / h_u_traj: the control (num_steps, num_timesteps, n); d_x_traj / h_x_traj: the states (num_steps+1, num_timesteps, 2n)",
+          "null after init_gridData; the rollout host wrappers call this themselves, a caller calls it first to get h_u_traj to fill; grows on demand, close_grid frees"]),
+    rows=[("u_traj", "NUM_JOINTS", "(S > 0 ? S : 1)*N"), ("x_traj", "2*NUM_JOINTS", "(S + 1)*N")])
+
+ROLLOUT_HOST = dict(
+    name="rollout", tag="ROLLOUT", x0=True,
+    doc=("Roll num_timesteps trajectories forward by num_steps steps (ABA forward dynamics + semi-implicit Euler)",
+         ["no counterpart in the reference; call rollout_reserve first and fill h_u_traj",
+          "_single_timing: solve 0 alone, num_steps steps in one launch, time per step printed; h_x_traj holds its (num_steps+1, 2n) trajectory"],
+         "x0 in h_q_qd_u (rows of 3n, [q | qd | unused]), u in h_u_traj (num_steps, num_timesteps, n), result in h_x_traj (num_steps+1, num_timesteps, 2n)", "takes"),
+    args="hd_data->d_x_traj,static_cast<T *>(nullptr),hd_data->d_q_qd_u,stride_x0,hd_data->d_u_traj,stride_u_step,stride_u_solve,d_robotModel,dt,gravity,num_timesteps,num_steps);",
+    h2d=[("q_qd_u", "stride_x0", ""), ("u_traj", "NUM_JOINTS", "*num_steps")],
+    d2h=[("x_traj", "2*NUM_JOINTS", "*(num_steps + 1)")])
+
+
 def gen_rollout_reserve(self):
-    self.gen_add_func_doc("Reserves the rollout buffers of hd_data for num_timesteps solves of num_steps steps (the reference's gridData has no such buffers)",
-                          ["d_u_traj / h_u_traj: the control (num_steps, num_timesteps, n); d_x_traj / h_x_traj: the states (num_steps+1, num_timesteps, 2n)",
-                           "null after init_gridData; the rollout host wrappers call this themselves, a caller calls it first to get h_u_traj to fill; grows on demand, close_grid frees"],
-                          ["hd_data is the packaged input and output pointers", "num_timesteps is the number of solves", "num_steps is the number of steps"], None)
-    self.gen_add_code_line("template <typename T>")
-    self.gen_add_code_line("__host__")
-    self.gen_add_code_line("void rollout_reserve(gridData<T> *hd_data, const int num_timesteps, const int num_steps) {", True)
-    self.gen_add_code_lines(["const int N = num_timesteps > 1 ? num_timesteps : 1; const int S = num_steps > 0 ? num_steps : 0;",
-                             "grid_ee_reserve<T>(&hd_data->d_u_traj, &hd_data->h_u_traj, NUM_JOINTS, (S > 0 ? S : 1)*N);",
-                             "grid_ee_reserve<T>(&hd_data->d_x_traj, &hd_data->h_x_traj, 2*NUM_JOINTS, (S + 1)*N);"])
-    self.gen_add_end_function()
+    gen_rollout_family_reserve(self, ROLLOUT_RESERVE)
 
 
 def gen_rollout_host(self, mode=0):
-    single_call_timing = mode == 1
-    compute_only = mode == 2
-    func_params = ["hd_data is the packaged input and output pointers: x0 in h_q_qd_u (rows of 3n, [q | qd | unused]), u in h_u_traj (num_steps, num_timesteps, n), result in h_x_traj (num_steps+1, num_timesteps, 2n)",
-                   "d_robotModel is the pointer to the initialized model specific helpers on the GPU (XImats, topology_helpers, etc.)",
-                   "dt is the time step", "gravity is the gravity constant,",
-                   "num_timesteps is the number of independent solves (trajectories)", "num_steps is the number of steps every solve takes",
-                   "streams are pointers to HIP streams for async memory transfers (if needed)"]
-    name = "rollout" + ("_single_timing" if single_call_timing else "") + ("_compute_only" if compute_only else "")
-    notes = ["no counterpart in the reference; call rollout_reserve first and fill h_u_traj",
-             "_single_timing: solve 0 alone, num_steps steps in one launch, time per step printed; h_x_traj holds its (num_steps+1, 2n) trajectory"] if mode == 0 else []
-    self.gen_add_func_doc("Roll num_timesteps trajectories forward by num_steps steps (ABA forward dynamics + semi-implicit Euler)", notes, func_params, None)
-    self.gen_add_code_line("template <typename T>")
-    self.gen_add_code_line("__host__")
-    self.gen_add_code_line("void " + name + "(gridData<T> *hd_data, const robotModel<T> *d_robotModel, const T dt, const T gravity, const int num_timesteps, const int num_steps,")
-    self.gen_add_code_line("                      const dim3 block_dimms, const dim3 thread_dimms" + ("" if compute_only else ", hipStream_t *streams") + ") {", True)
-    N = "1" if single_call_timing else "num_timesteps"
-    self.gen_add_code_lines(["rollout_reserve<T>(hd_data, %s, num_steps);" % N,
-                             "const int stride_x0 = 3*NUM_JOINTS; const int stride_u_solve = NUM_JOINTS; const long stride_u_step = static_cast<long>(NUM_JOINTS)*%s;" % N])
-    if not compute_only:
-        self.gen_add_code_lines(["// start code with memory transfer",
-                                 "gpuErrchk(hipMemcpyAsync(hd_data->d_q_qd_u,hd_data->h_q_qd_u,static_cast<size_t>(stride_x0)*" + N + "*sizeof(T),hipMemcpyHostToDevice,streams[0]));",
-                                 "gpuErrchk(hipMemcpyAsync(hd_data->d_u_traj,hd_data->h_u_traj,static_cast<size_t>(NUM_JOINTS)*" + N + "*num_steps*sizeof(T),hipMemcpyHostToDevice,streams[0]));",
-                                 "gpuErrchk(hipDeviceSynchronize());"])
-    kern = "rollout_kernel" + ("_single_timing" if single_call_timing else "") + "<T>"
-    self.gen_add_code_line("// then call the kernel")
-    if single_call_timing:
-        self.gen_add_code_line("struct timespec start, end; clock_gettime(CLOCK_MONOTONIC,&start);")
-    self.gen_add_code_lines(["hipLaunchKernelGGL((" + kern + "),block_dimms,thread_dimms,grid_lds_bytes<T>(thread_dimms, ROLLOUT_LDS_PER_SOLVE, ROLLOUT_OUT_PER_SOLVE),0,hd_data->d_x_traj,static_cast<T *>(nullptr),"
-                             "hd_data->d_q_qd_u,stride_x0,hd_data->d_u_traj,stride_u_step,stride_u_solve,d_robotModel,dt,gravity,num_timesteps,num_steps);",
-                             "gpuErrchk(hipGetLastError()); gpuErrchk(hipDeviceSynchronize());"])
-    if single_call_timing:
-        self.gen_add_code_line("clock_gettime(CLOCK_MONOTONIC,&end);")
-    if not compute_only:
-        self.gen_add_code_lines(["// finally transfer the result back",
-                                 "gpuErrchk(hipMemcpy(hd_data->h_x_traj,hd_data->d_x_traj,static_cast<size_t>(2*NUM_JOINTS)*" + N + "*(num_steps + 1)*sizeof(T),hipMemcpyDeviceToHost));",
-                                 "gpuErrchk(hipDeviceSynchronize());"])
-    if single_call_timing:
-        self.gen_add_code_line("printf(\"Single Call ROLLOUT %fus\\n\",time_delta_us_timespec(start,end)/static_cast<double>(num_steps > 0 ? num_steps : 1));")
-    self.gen_add_end_function()
+    gen_rollout_family_host(self, ROLLOUT_HOST, mode)
 
 
 def gen_rollout(self, use_thread_group=False):

@@ -18,7 +18,7 @@ LDS: the slice of rollout_linearized with lam (2n) and w (n) behind it; staging:
 grad_u_t and grad_x0 pass through the head of the wave's first image).  The linearisation is rollout_linearize_device: the inner calls of
 rollout_linearized_device without its state update (that function keeps its text; the adjoint does not call it).
 """
-from ._rollout_linearized import _gen_save, _pad4
+from ._rollout_common import _pad4, gen_rollout_family_host, gen_rollout_family_reserve, gen_rollout_kernel_head, gen_rollout_save, gen_rollout_step_loop
 
 
 def gen_rollout_adjoint_layout(self):
@@ -177,14 +177,7 @@ def gen_rollout_adjoint_kernel(self, use_thread_group=False, single_call_timing=
                              "T *s_fx = &s_out_all[grp*%d];" % (2 * n * n),
                              "T *s_gu = &s_out_all[(grp & ~(GRID_SOLVES_PER_WAVE-1))*%d + (grp & (GRID_SOLVES_PER_WAVE-1))*%d];" % (2 * n * n, n),
                              "T *s_out = &s_out_all[(grp & ~(GRID_SOLVES_PER_WAVE-1))*%d + (grp & (GRID_SOLVES_PER_WAVE-1))*%d];" % (2 * n * n, 2 * n)])
-    if single_call_timing:
-        self.gen_add_code_line("const int k = 0; const int kc = 0; const bool valid = (blockIdx.x + blockIdx.y == 0) && (grp == 0); const int lane = lane_id; (void)k; (void)NUM_TIMESTEPS;")
-        self.gen_add_code_line("const size_t row_stride = %d; const size_t gu_stride = %d;" % (2 * n, n))
-        self.gen_add_code_line("if (!valid) {return;}")
-    else:
-        self.gen_add_parallel_loop("k", "NUM_TIMESTEPS", use_thread_group, block_level=True)
-        self.gen_add_code_line("// elements between two time slices of d_traj / d_gx, d_grad_u")
-        self.gen_add_code_line("const size_t row_stride = static_cast<size_t>(NUM_TIMESTEPS)*%d; const size_t gu_stride = static_cast<size_t>(NUM_TIMESTEPS)*%d; (void)valid;" % (2 * n, n))
+    gen_rollout_kernel_head(self, [("row", 2 * n), ("gu", n)], "d_traj / d_gx, d_grad_u", single_call_timing, use_thread_group, valid_unused=True)
     self.gen_add_code_line("// lam_T = g_T (+ gxT) and the row of step T-1: [q | qd] of d_traj, u")
     self.gen_add_code_line("if (lane < %d) {" % n, True)
     self.gen_add_code_line("const size_t xk = static_cast<size_t>(kc)*%d + lane;" % (2 * n))
@@ -198,8 +191,7 @@ def gen_rollout_adjoint_kernel(self, use_thread_group=False, single_call_timing=
     self.gen_add_code_line("s_lam[lane] = lq; s_lam[%d + lane] = lv;" % n)
     self.gen_add_end_control_flow()
     self.gen_add_sync(use_thread_group)
-    self.gen_add_code_line("for (int t = NUM_STEPS - 1; t >= 0; t--){", True)
-    self.gen_add_code_line("const int lane = grid_loop_variant(lane_id); // (shadows the outer one: keeps lane-dependent values from being hoisted out of the step loop and spilled)")
+    gen_rollout_step_loop(self, reverse=True)
     prefetch = self.gen_rollout_adjoint_prefetch()
     kk = "kc" if single_call_timing else "(k < NUM_TIMESTEPS ? k : NUM_TIMESTEPS - 1)"
 
@@ -225,78 +217,45 @@ def gen_rollout_adjoint_kernel(self, use_thread_group=False, single_call_timing=
         load_row()
         self.gen_add_code_line("rollout_adjoint_contract_device<T>(s_gu, s_lam, s_w, s_fx, &s_mem[ROLLOUT_LIN_OFF_MINV], dt, lane, r_gq, r_gv, d_grad_u != nullptr);")
     self.gen_add_code_line("if (d_grad_u != nullptr) {", True)
-    _gen_save(self, "d_grad_u + static_cast<size_t>(t)*gu_stride", "gu_t", n, "s_gu", single_call_timing, use_thread_group)
+    gen_rollout_save(self, "d_grad_u + static_cast<size_t>(t)*gu_stride", "gu_t", n, "s_gu", single_call_timing, use_thread_group)
     self.gen_add_end_control_flow()
     self.gen_add_code_line("if (t > 0 && lane < %d) { s_q[lane] = r_q; s_qd[lane] = r_qd; s_tau[lane] = r_u; }" % n)
     self.gen_add_sync(use_thread_group)
     self.gen_add_end_control_flow()
     self.gen_add_code_line("if (d_grad_x0 != nullptr) { // lam_0", True)
-    _gen_save(self, "d_grad_x0", "gx0_k", 2 * n, "s_out", single_call_timing, use_thread_group, "s_lam")
+    gen_rollout_save(self, "d_grad_x0", "gx0_k", 2 * n, "s_out", single_call_timing, use_thread_group, "s_lam")
     self.gen_add_end_control_flow()
     if not single_call_timing:
         self.gen_add_end_control_flow()
     self.gen_add_end_function()
 
 
+ROLLOUT_ADJOINT_RESERVE = dict(
+    name="rollout_adjoint", base="rollout", min_steps=0,
+    doc=("Reserves the buffers of the rollout adjoint for num_timesteps solves of num_steps steps (those of rollout_reserve, the cotangent of the trajectory and the two gradients)",
+         ["d_gx_traj / h_gx_traj: (num_steps+1, num_timesteps, 2n); d_gu_traj / h_gu_traj: (num_steps, num_timesteps, n); d_gx0 / h_gx0: (num_timesteps, 2n)",
+          "null after init_gridData; the rollout_adjoint host wrappers call this themselves; grows on demand, close_grid frees"]),
+    rows=[("gx_traj", "2*NUM_JOINTS", "(S + 1)*N"), ("gu_traj", "NUM_JOINTS", "(S > 0 ? S : 1)*N"), ("gx0", "2*NUM_JOINTS", "N")])
+
+ROLLOUT_ADJOINT_HOST = dict(
+    name="rollout_adjoint", tag="ROLLOUT_ADJ", x0=False,
+    doc=("Walk num_timesteps trajectories backwards by num_steps steps and return the gradient of a trajectory cost with respect to x0 and every control",
+         ["no counterpart in the reference; call rollout_adjoint_reserve first and fill h_x_traj (rollout leaves its result there), h_u_traj and h_gx_traj",
+          "_single_timing: solve 0 alone, num_steps steps in one launch, time per step printed"],
+         "the trajectory in h_x_traj (num_steps+1, num_timesteps, 2n), u in h_u_traj (num_steps, num_timesteps, n), "
+         "d cost / d traj in h_gx_traj (num_steps+1, num_timesteps, 2n); results in h_gx0 (num_timesteps, 2n) and h_gu_traj (num_steps, num_timesteps, n)", "took"),
+    args="hd_data->d_gx0,hd_data->d_gu_traj,hd_data->d_x_traj,hd_data->d_u_traj,stride_u_step,stride_u_solve,hd_data->d_gx_traj,static_cast<const T *>(nullptr),"
+         "d_robotModel,dt,gravity,num_timesteps,num_steps);",
+    h2d=[("x_traj", "2*NUM_JOINTS", "*(num_steps + 1)"), ("gx_traj", "2*NUM_JOINTS", "*(num_steps + 1)"), ("u_traj", "NUM_JOINTS", "*num_steps")],
+    d2h=[("gx0", "2*NUM_JOINTS", ""), ("gu_traj", "NUM_JOINTS", "*num_steps")])
+
+
 def gen_rollout_adjoint_reserve(self):
-    self.gen_add_func_doc("Reserves the buffers of the rollout adjoint for num_timesteps solves of num_steps steps (those of rollout_reserve, the cotangent of the trajectory and the two gradients)",
-                          ["d_gx_traj / h_gx_traj: (num_steps+1, num_timesteps, 2n); d_gu_traj / h_gu_traj: (num_steps, num_timesteps, n); d_gx0 / h_gx0: (num_timesteps, 2n)",
-                           "null after init_gridData; the rollout_adjoint host wrappers call this themselves; grows on demand, close_grid frees"],
-                          ["hd_data is the packaged input and output pointers", "num_timesteps is the number of solves", "num_steps is the number of steps"], None)
-    self.gen_add_code_line("template <typename T>")
-    self.gen_add_code_line("__host__")
-    self.gen_add_code_line("void rollout_adjoint_reserve(gridData<T> *hd_data, const int num_timesteps, const int num_steps) {", True)
-    self.gen_add_code_lines(["rollout_reserve<T>(hd_data, num_timesteps, num_steps);",
-                             "const int N = num_timesteps > 1 ? num_timesteps : 1; const int S = num_steps > 0 ? num_steps : 0;",
-                             "grid_ee_reserve<T>(&hd_data->d_gx_traj, &hd_data->h_gx_traj, 2*NUM_JOINTS, (S + 1)*N);",
-                             "grid_ee_reserve<T>(&hd_data->d_gu_traj, &hd_data->h_gu_traj, NUM_JOINTS, (S > 0 ? S : 1)*N);",
-                             "grid_ee_reserve<T>(&hd_data->d_gx0, &hd_data->h_gx0, 2*NUM_JOINTS, N);"])
-    self.gen_add_end_function()
+    gen_rollout_family_reserve(self, ROLLOUT_ADJOINT_RESERVE)
 
 
 def gen_rollout_adjoint_host(self, mode=0):
-    single_call_timing = mode == 1
-    compute_only = mode == 2
-    func_params = ["hd_data is the packaged input and output pointers: the trajectory in h_x_traj (num_steps+1, num_timesteps, 2n), u in h_u_traj (num_steps, num_timesteps, n), "
-                   "d cost / d traj in h_gx_traj (num_steps+1, num_timesteps, 2n); results in h_gx0 (num_timesteps, 2n) and h_gu_traj (num_steps, num_timesteps, n)",
-                   "d_robotModel is the pointer to the initialized model specific helpers on the GPU (XImats, topology_helpers, etc.)",
-                   "dt is the time step", "gravity is the gravity constant,",
-                   "num_timesteps is the number of independent solves (trajectories)", "num_steps is the number of steps every solve took",
-                   "streams are pointers to HIP streams for async memory transfers (if needed)"]
-    name = "rollout_adjoint" + ("_single_timing" if single_call_timing else "") + ("_compute_only" if compute_only else "")
-    notes = ["no counterpart in the reference; call rollout_adjoint_reserve first and fill h_x_traj (rollout leaves its result there), h_u_traj and h_gx_traj",
-             "_single_timing: solve 0 alone, num_steps steps in one launch, time per step printed"] if mode == 0 else []
-    self.gen_add_func_doc("Walk num_timesteps trajectories backwards by num_steps steps and return the gradient of a trajectory cost with respect to x0 and every control", notes, func_params, None)
-    self.gen_add_code_line("template <typename T>")
-    self.gen_add_code_line("__host__")
-    self.gen_add_code_line("void " + name + "(gridData<T> *hd_data, const robotModel<T> *d_robotModel, const T dt, const T gravity, const int num_timesteps, const int num_steps,")
-    self.gen_add_code_line("                      const dim3 block_dimms, const dim3 thread_dimms" + ("" if compute_only else ", hipStream_t *streams") + ") {", True)
-    N = "1" if single_call_timing else "num_timesteps"
-    self.gen_add_code_lines(["rollout_adjoint_reserve<T>(hd_data, %s, num_steps);" % N,
-                             "const int stride_u_solve = NUM_JOINTS; const long stride_u_step = static_cast<long>(NUM_JOINTS)*%s;" % N])
-    if not compute_only:
-        self.gen_add_code_lines(["// start code with memory transfer",
-                                 "gpuErrchk(hipMemcpyAsync(hd_data->d_x_traj,hd_data->h_x_traj,static_cast<size_t>(2*NUM_JOINTS)*" + N + "*(num_steps + 1)*sizeof(T),hipMemcpyHostToDevice,streams[0]));",
-                                 "gpuErrchk(hipMemcpyAsync(hd_data->d_gx_traj,hd_data->h_gx_traj,static_cast<size_t>(2*NUM_JOINTS)*" + N + "*(num_steps + 1)*sizeof(T),hipMemcpyHostToDevice,streams[0]));",
-                                 "gpuErrchk(hipMemcpyAsync(hd_data->d_u_traj,hd_data->h_u_traj,static_cast<size_t>(NUM_JOINTS)*" + N + "*num_steps*sizeof(T),hipMemcpyHostToDevice,streams[0]));",
-                                 "gpuErrchk(hipDeviceSynchronize());"])
-    kern = "rollout_adjoint_kernel" + ("_single_timing" if single_call_timing else "") + "<T>"
-    self.gen_add_code_line("// then call the kernel")
-    if single_call_timing:
-        self.gen_add_code_line("struct timespec start, end; clock_gettime(CLOCK_MONOTONIC,&start);")
-    self.gen_add_code_lines(["hipLaunchKernelGGL((" + kern + "),block_dimms,thread_dimms,grid_lds_bytes<T>(thread_dimms, ROLLOUT_ADJ_LDS_PER_SOLVE, ROLLOUT_ADJ_OUT_PER_SOLVE),0,hd_data->d_gx0,hd_data->d_gu_traj,"
-                             "hd_data->d_x_traj,hd_data->d_u_traj,stride_u_step,stride_u_solve,hd_data->d_gx_traj,static_cast<const T *>(nullptr),d_robotModel,dt,gravity,num_timesteps,num_steps);",
-                             "gpuErrchk(hipGetLastError()); gpuErrchk(hipDeviceSynchronize());"])
-    if single_call_timing:
-        self.gen_add_code_line("clock_gettime(CLOCK_MONOTONIC,&end);")
-    if not compute_only:
-        self.gen_add_code_lines(["// finally transfer the results back",
-                                 "gpuErrchk(hipMemcpy(hd_data->h_gx0,hd_data->d_gx0,static_cast<size_t>(2*NUM_JOINTS)*" + N + "*sizeof(T),hipMemcpyDeviceToHost));",
-                                 "gpuErrchk(hipMemcpy(hd_data->h_gu_traj,hd_data->d_gu_traj,static_cast<size_t>(NUM_JOINTS)*" + N + "*num_steps*sizeof(T),hipMemcpyDeviceToHost));",
-                                 "gpuErrchk(hipDeviceSynchronize());"])
-    if single_call_timing:
-        self.gen_add_code_line("printf(\"Single Call ROLLOUT_ADJ %fus\\n\",time_delta_us_timespec(start,end)/static_cast<double>(num_steps > 0 ? num_steps : 1));")
-    self.gen_add_end_function()
+    gen_rollout_family_host(self, ROLLOUT_ADJOINT_HOST, mode)
 
 
 def gen_rollout_adjoint(self, use_thread_group=False):

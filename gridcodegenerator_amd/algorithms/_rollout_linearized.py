@@ -23,10 +23,8 @@ LDS: tip frame / column walk / long chains use the general slice; branched robot
 slice overlaid, M^-1 behind them).  ONE staging image of 2n^2 values per solve: fx is assembled in it and stored, fu is gathered straight from M^-1 by
 the solve's own lanes (16-byte pieces, mirrored from one triangle), then the state row passes through the head of the wave's image.
 """
-
-
-def _pad4(x):
-    return (x + 3) // 4 * 4
+from ._rollout_common import _pad4, gen_rollout_commit_control, gen_rollout_family_host, gen_rollout_family_reserve, gen_rollout_kernel_head, gen_rollout_load_x0, \
+    gen_rollout_prefetch_control, gen_rollout_save, gen_rollout_step_loop
 
 
 def gen_rollout_linearized_layout(self):
@@ -102,28 +100,6 @@ def gen_rollout_linearized_device(self, use_thread_group=False):
     self.gen_add_end_function()
 
 
-def _gen_save(self, row_ptr_expr, name, amount, src, single_call_timing, use_thread_group, copy_from=None):
-    """Stores the wave's records of `amount` values (staged at `src`, contiguous over the wave's lane groups) to `row_ptr_expr` (a T* to record 0 of the time slice);
-    copy_from: LDS vector staged into src first."""
-    if not single_call_timing:
-        # (as in rollout_kernel: opaque copies of the saver's invariants, so that its addresses are rebuilt per row instead of living in VGPRs across the dynamics)
-        self.gen_add_code_line("const int tid_t = grid_loop_variant(tid); const int grp_t = grid_loop_variant(grp); const int k_t = grid_loop_variant(k);")
-        self.gen_add_code_line("{ const int tid = tid_t; const int grp = grp_t; const int k = k_t; (void)tid; // (shadow the invariants)", True)
-    else:
-        self.gen_add_code_line("{", True)
-    self.gen_add_code_line("T *d_%s = %s;" % (name, row_ptr_expr))
-    if copy_from is not None:
-        self.gen_add_parallel_loop("ind", str(amount), use_thread_group)
-        self.gen_add_code_line("%s[ind] = %s[ind];" % (src, copy_from))
-        self.gen_add_end_control_flow()
-    if single_call_timing:
-        self.gen_kernel_save_result_single_timing(name, amount, use_thread_group, src)
-        self.gen_add_sync(use_thread_group)
-    else:
-        self.gen_kernel_save_result(name, amount, amount, use_thread_group, src)
-    self.gen_add_end_control_flow()
-
-
 def gen_rollout_linearized_kernel(self, use_thread_group=False, single_call_timing=False):
     n = self.model.n
     ld = self.minv_ld
@@ -158,29 +134,18 @@ def gen_rollout_linearized_kernel(self, use_thread_group=False, single_call_timi
                              "// the staging image of this solve; the state row goes through the head of the image of the wave's first solve (images of other waves are never touched)",
                              "T *s_fx = &s_out_all[grp*%d];" % (2 * n * n),
                              "T *s_out = &s_out_all[(grp & ~(GRID_SOLVES_PER_WAVE-1))*%d + (grp & (GRID_SOLVES_PER_WAVE-1))*%d];" % (2 * n * n, 2 * n)])
-    if single_call_timing:
-        self.gen_add_code_line("const int k = 0; const int kc = 0; const bool valid = (blockIdx.x + blockIdx.y == 0) && (grp == 0); const int lane = lane_id; (void)k; (void)NUM_TIMESTEPS;")
-        self.gen_add_code_line("const size_t row_stride = %d; const size_t fx_stride = %d; const size_t fu_stride = %d;" % (2 * n, 2 * n * n, n * n))
-        self.gen_add_code_line("if (!valid) {return;}")
-    else:
-        self.gen_add_parallel_loop("k", "NUM_TIMESTEPS", use_thread_group, block_level=True)
-        self.gen_add_code_line("// elements between two time slices of d_traj, d_fx, d_fu")
-        self.gen_add_code_line("const size_t row_stride = static_cast<size_t>(NUM_TIMESTEPS)*%d; const size_t fx_stride = static_cast<size_t>(NUM_TIMESTEPS)*%d; const size_t fu_stride = static_cast<size_t>(NUM_TIMESTEPS)*%d;" % (2 * n, 2 * n * n, n * n))
-    self.gen_add_code_line("T r_u = (NUM_STEPS > 0 && lane < %d) ? d_u[kc*stride_u_solve + lane] : static_cast<T>(0); // control of step 0, in flight while x0 arrives" % n)
-    self.gen_kernel_load_inputs("x0", "stride_x0", 2 * n, use_thread_group)
-    self.gen_add_code_line("if (lane < %d) { s_tau[lane] = r_u; }" % n)
-    self.gen_add_sync(use_thread_group)
+    gen_rollout_kernel_head(self, [("row", 2 * n), ("fx", 2 * n * n), ("fu", n * n)], "d_traj, d_fx, d_fu", single_call_timing, use_thread_group)
+    gen_rollout_load_x0(self, use_thread_group)
+    save = lambda row_ptr_expr, name, amount, src, copy_from=None: gen_rollout_save(self, row_ptr_expr, name, amount, src, single_call_timing, use_thread_group, copy_from)
     self.gen_add_code_line("if (d_traj != nullptr) { // row 0 is x0", True)
-    _gen_save(self, "d_traj", "traj_t", 2 * n, "s_out", single_call_timing, use_thread_group, "s_x")
+    save("d_traj", "traj_t", 2 * n, "s_out", "s_x")
     self.gen_add_end_control_flow()
-    self.gen_add_code_line("for (int t = 0; t < NUM_STEPS; t++){", True)
-    self.gen_add_code_line("const int lane = grid_loop_variant(lane_id); // (shadows the outer one: keeps lane-dependent values from being hoisted out of the step loop and spilled)")
+    gen_rollout_step_loop(self)
     self.gen_add_code_line("// the next step's control leaves for the registers now and lands in LDS after this step (no pointer is kept alive across the dynamics)")
-    self.gen_add_code_line("const T *d_u_t = d_u + static_cast<long>(t + 1)*stride_u_step;")
-    self.gen_add_code_line("r_u = (t + 1 < NUM_STEPS && lane < %d) ? d_u_t[%s*stride_u_solve + lane] : static_cast<T>(0);" % (n, "kc" if single_call_timing else "(k < NUM_TIMESTEPS ? k : NUM_TIMESTEPS - 1)"))
+    gen_rollout_prefetch_control(self, single_call_timing)
     self.gen_add_code_line("rollout_linearized_device<T>(s_fx, s_q, s_qd, s_tau, s_mem, d_robotModel, dt, gravity, lane, d_fu != nullptr);")
     self.gen_add_code_line("if (d_fx != nullptr) {", True)
-    _gen_save(self, "d_fx + static_cast<size_t>(t)*fx_stride", "fx_t", 2 * n * n, "s_fx", single_call_timing, use_thread_group)
+    save("d_fx + static_cast<size_t>(t)*fx_stride", "fx_t", 2 * n * n, "s_fx")
     self.gen_add_end_control_flow()
     self.gen_add_code_line("if (d_fu != nullptr && valid) { // dense symmetric record gathered from one triangle of M^-1 by the solve's own lanes: no staging copy", True)
     self.gen_add_code_line("T *dst = d_fu + static_cast<size_t>(t)*fu_stride + static_cast<size_t>(%s)*%d;" % ("kc" if single_call_timing else "grid_loop_variant(k)", n * n))
@@ -194,78 +159,45 @@ def gen_rollout_linearized_kernel(self, use_thread_group=False, single_call_timi
         self.gen_add_code_line("{ const int ind = %d + lane; if (lane < %d) { const int row = ind %% %d; const int col = ind / %d; dst[ind] = (row <= col) ? s_Minv[col*%d + row] : s_Minv[row*%d + col]; } }"
                                % (n * n // 4 * 4, (n * n) % 4, n, n, ld, ld))
     self.gen_add_end_control_flow()
-    self.gen_add_code_line("if (lane < %d) { s_tau[lane] = r_u; }" % n)
-    self.gen_add_sync(use_thread_group)
+    gen_rollout_commit_control(self, use_thread_group)
     self.gen_add_code_line("if (d_traj != nullptr) {", True)
-    _gen_save(self, "d_traj + static_cast<size_t>(t + 1)*row_stride", "traj_t", 2 * n, "s_out", single_call_timing, use_thread_group, "s_x")
+    save("d_traj + static_cast<size_t>(t + 1)*row_stride", "traj_t", 2 * n, "s_out", "s_x")
     self.gen_add_end_control_flow()
     self.gen_add_end_control_flow()
     self.gen_add_code_line("if (d_xT != nullptr) {", True)
-    _gen_save(self, "d_xT", "xT_k", 2 * n, "s_out", single_call_timing, use_thread_group, "s_x")
+    save("d_xT", "xT_k", 2 * n, "s_out", "s_x")
     self.gen_add_end_control_flow()
     if not single_call_timing:
         self.gen_add_end_control_flow()
     self.gen_add_end_function()
 
 
+ROLLOUT_LINEARIZED_RESERVE = dict(
+    name="rollout_linearized", base="rollout", min_steps=1,
+    doc=("Reserves the buffers of the linearised rollout for num_timesteps solves of num_steps steps (those of rollout_reserve and the two Jacobian records)",
+         ["d_fx_traj / h_fx_traj: (num_steps, num_timesteps, 2n^2); d_fu_traj / h_fu_traj: (num_steps, num_timesteps, n^2)",
+          "null after init_gridData; the rollout_linearized host wrappers call this themselves; grows on demand, close_grid frees"]),
+    rows=[("fx_traj", "2*NUM_JOINTS*NUM_JOINTS", "S*N"), ("fu_traj", "NUM_JOINTS*NUM_JOINTS", "S*N")])
+
+ROLLOUT_LINEARIZED_HOST = dict(
+    name="rollout_linearized", tag="ROLLOUT_LIN", x0=True,
+    doc=("Roll num_timesteps trajectories forward by num_steps steps and return the Jacobians of the dynamics at every step",
+         ["no counterpart in the reference; call rollout_linearized_reserve first and fill h_u_traj",
+          "_single_timing: solve 0 alone, num_steps steps in one launch, time per step printed"],
+         "x0 in h_q_qd_u (rows of 3n, [q | qd | unused]), u in h_u_traj (num_steps, num_timesteps, n); "
+         "results in h_x_traj (num_steps+1, num_timesteps, 2n), h_fx_traj (num_steps, num_timesteps, 2n^2), h_fu_traj (num_steps, num_timesteps, n^2)", "takes"),
+    args="hd_data->d_x_traj,static_cast<T *>(nullptr),hd_data->d_fx_traj,hd_data->d_fu_traj,hd_data->d_q_qd_u,stride_x0,hd_data->d_u_traj,stride_u_step,stride_u_solve,"
+         "d_robotModel,dt,gravity,num_timesteps,num_steps);",
+    h2d=[("q_qd_u", "stride_x0", ""), ("u_traj", "NUM_JOINTS", "*num_steps")],
+    d2h=[("x_traj", "2*NUM_JOINTS", "*(num_steps + 1)"), ("fx_traj", "2*NUM_JOINTS*NUM_JOINTS", "*num_steps"), ("fu_traj", "NUM_JOINTS*NUM_JOINTS", "*num_steps")])
+
+
 def gen_rollout_linearized_reserve(self):
-    self.gen_add_func_doc("Reserves the buffers of the linearised rollout for num_timesteps solves of num_steps steps (those of rollout_reserve and the two Jacobian records)",
-                          ["d_fx_traj / h_fx_traj: (num_steps, num_timesteps, 2n^2); d_fu_traj / h_fu_traj: (num_steps, num_timesteps, n^2)",
-                           "null after init_gridData; the rollout_linearized host wrappers call this themselves; grows on demand, close_grid frees"],
-                          ["hd_data is the packaged input and output pointers", "num_timesteps is the number of solves", "num_steps is the number of steps"], None)
-    self.gen_add_code_line("template <typename T>")
-    self.gen_add_code_line("__host__")
-    self.gen_add_code_line("void rollout_linearized_reserve(gridData<T> *hd_data, const int num_timesteps, const int num_steps) {", True)
-    self.gen_add_code_lines(["rollout_reserve<T>(hd_data, num_timesteps, num_steps);",
-                             "const int N = num_timesteps > 1 ? num_timesteps : 1; const int S = num_steps > 0 ? num_steps : 1;",
-                             "grid_ee_reserve<T>(&hd_data->d_fx_traj, &hd_data->h_fx_traj, 2*NUM_JOINTS*NUM_JOINTS, S*N);",
-                             "grid_ee_reserve<T>(&hd_data->d_fu_traj, &hd_data->h_fu_traj, NUM_JOINTS*NUM_JOINTS, S*N);"])
-    self.gen_add_end_function()
+    gen_rollout_family_reserve(self, ROLLOUT_LINEARIZED_RESERVE)
 
 
 def gen_rollout_linearized_host(self, mode=0):
-    single_call_timing = mode == 1
-    compute_only = mode == 2
-    func_params = ["hd_data is the packaged input and output pointers: x0 in h_q_qd_u (rows of 3n, [q | qd | unused]), u in h_u_traj (num_steps, num_timesteps, n); "
-                   "results in h_x_traj (num_steps+1, num_timesteps, 2n), h_fx_traj (num_steps, num_timesteps, 2n^2), h_fu_traj (num_steps, num_timesteps, n^2)",
-                   "d_robotModel is the pointer to the initialized model specific helpers on the GPU (XImats, topology_helpers, etc.)",
-                   "dt is the time step", "gravity is the gravity constant,",
-                   "num_timesteps is the number of independent solves (trajectories)", "num_steps is the number of steps every solve takes",
-                   "streams are pointers to HIP streams for async memory transfers (if needed)"]
-    name = "rollout_linearized" + ("_single_timing" if single_call_timing else "") + ("_compute_only" if compute_only else "")
-    notes = ["no counterpart in the reference; call rollout_linearized_reserve first and fill h_u_traj",
-             "_single_timing: solve 0 alone, num_steps steps in one launch, time per step printed"] if mode == 0 else []
-    self.gen_add_func_doc("Roll num_timesteps trajectories forward by num_steps steps and return the Jacobians of the dynamics at every step", notes, func_params, None)
-    self.gen_add_code_line("template <typename T>")
-    self.gen_add_code_line("__host__")
-    self.gen_add_code_line("void " + name + "(gridData<T> *hd_data, const robotModel<T> *d_robotModel, const T dt, const T gravity, const int num_timesteps, const int num_steps,")
-    self.gen_add_code_line("                      const dim3 block_dimms, const dim3 thread_dimms" + ("" if compute_only else ", hipStream_t *streams") + ") {", True)
-    N = "1" if single_call_timing else "num_timesteps"
-    self.gen_add_code_lines(["rollout_linearized_reserve<T>(hd_data, %s, num_steps);" % N,
-                             "const int stride_x0 = 3*NUM_JOINTS; const int stride_u_solve = NUM_JOINTS; const long stride_u_step = static_cast<long>(NUM_JOINTS)*%s;" % N])
-    if not compute_only:
-        self.gen_add_code_lines(["// start code with memory transfer",
-                                 "gpuErrchk(hipMemcpyAsync(hd_data->d_q_qd_u,hd_data->h_q_qd_u,static_cast<size_t>(stride_x0)*" + N + "*sizeof(T),hipMemcpyHostToDevice,streams[0]));",
-                                 "gpuErrchk(hipMemcpyAsync(hd_data->d_u_traj,hd_data->h_u_traj,static_cast<size_t>(NUM_JOINTS)*" + N + "*num_steps*sizeof(T),hipMemcpyHostToDevice,streams[0]));",
-                                 "gpuErrchk(hipDeviceSynchronize());"])
-    kern = "rollout_linearized_kernel" + ("_single_timing" if single_call_timing else "") + "<T>"
-    self.gen_add_code_line("// then call the kernel")
-    if single_call_timing:
-        self.gen_add_code_line("struct timespec start, end; clock_gettime(CLOCK_MONOTONIC,&start);")
-    self.gen_add_code_lines(["hipLaunchKernelGGL((" + kern + "),block_dimms,thread_dimms,grid_lds_bytes<T>(thread_dimms, ROLLOUT_LIN_LDS_PER_SOLVE, ROLLOUT_LIN_OUT_PER_SOLVE),0,hd_data->d_x_traj,static_cast<T *>(nullptr),"
-                             "hd_data->d_fx_traj,hd_data->d_fu_traj,hd_data->d_q_qd_u,stride_x0,hd_data->d_u_traj,stride_u_step,stride_u_solve,d_robotModel,dt,gravity,num_timesteps,num_steps);",
-                             "gpuErrchk(hipGetLastError()); gpuErrchk(hipDeviceSynchronize());"])
-    if single_call_timing:
-        self.gen_add_code_line("clock_gettime(CLOCK_MONOTONIC,&end);")
-    if not compute_only:
-        self.gen_add_code_lines(["// finally transfer the results back",
-                                 "gpuErrchk(hipMemcpy(hd_data->h_x_traj,hd_data->d_x_traj,static_cast<size_t>(2*NUM_JOINTS)*" + N + "*(num_steps + 1)*sizeof(T),hipMemcpyDeviceToHost));",
-                                 "gpuErrchk(hipMemcpy(hd_data->h_fx_traj,hd_data->d_fx_traj,static_cast<size_t>(2*NUM_JOINTS*NUM_JOINTS)*" + N + "*num_steps*sizeof(T),hipMemcpyDeviceToHost));",
-                                 "gpuErrchk(hipMemcpy(hd_data->h_fu_traj,hd_data->d_fu_traj,static_cast<size_t>(NUM_JOINTS*NUM_JOINTS)*" + N + "*num_steps*sizeof(T),hipMemcpyDeviceToHost));",
-                                 "gpuErrchk(hipDeviceSynchronize());"])
-    if single_call_timing:
-        self.gen_add_code_line("printf(\"Single Call ROLLOUT_LIN %fus\\n\",time_delta_us_timespec(start,end)/static_cast<double>(num_steps > 0 ? num_steps : 1));")
-    self.gen_add_end_function()
+    gen_rollout_family_host(self, ROLLOUT_LINEARIZED_HOST, mode)
 
 
 def gen_rollout_linearized(self, use_thread_group=False):

@@ -19,8 +19,11 @@ struct grid_capi_error {
 #include <limits.h>
 #include <string.h>
 
+#include <algorithm>
+#include <initializer_list>
 #include <mutex>
 #include <new>
+#include <optional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -134,44 +137,57 @@ namespace grid_so = grid::wide;
 namespace grid_so = grid;
 #endif
 
+// what the launch geometry of one kernel is derived from: the constants the generated header emits beside it.  threads: its suggested block size; max_groups: the
+// lane groups per block it serves (it retires the rest); lds, out: elements of one solve's LDS slice and of its output staging; lanes: lanes of one lane group
+struct kernel_shape {
+    int threads, max_groups, lds, out, lanes;
+};
+namespace shape {
+constexpr kernel_shape outer(int threads, int lds, int out) { return {threads, grid::GRID_MAX_SOLVES_PER_BLOCK, lds, out, grid::GRID_LANES_PER_SOLVE}; }
+constexpr kernel_shape GENERAL = outer(grid::SUGGESTED_THREADS, grid::GRID_LDS_PER_SOLVE, grid::GRID_OUT_PER_SOLVE);  // the kernels without a slice of their own
+// forward_dynamics_gradient_kernel has its own (smaller) LDS slice and suggested block size
+constexpr kernel_shape FD_DU = outer(grid::FD_DU_SUGGESTED_THREADS, grid::FD_DU_LDS_PER_SOLVE, grid::FD_DU_OUT_PER_SOLVE);
+constexpr kernel_shape ID = outer(grid::ID_SUGGESTED_THREADS, grid::ID_LDS_PER_SOLVE, grid::ID_OUT_PER_SOLVE);
+constexpr kernel_shape ID_DU = outer(grid::ID_DU_SUGGESTED_THREADS, grid::ID_DU_LDS_PER_SOLVE, grid::ID_DU_OUT_PER_SOLVE);
+constexpr kernel_shape MINV = outer(grid::MINV_SUGGESTED_THREADS, grid::MINV_LDS_PER_SOLVE, grid::MINV_OUT_PER_SOLVE);
+constexpr kernel_shape FD = outer(grid::FD_SUGGESTED_THREADS, grid::FD_LDS_PER_SOLVE, grid::FD_OUT_PER_SOLVE);
+constexpr kernel_shape ABA = outer(grid::ABA_SUGGESTED_THREADS, grid::ABA_LDS_PER_SOLVE, grid::ABA_OUT_PER_SOLVE);
+constexpr kernel_shape CRBA = outer(grid::CRBA_SUGGESTED_THREADS, grid::CRBA_LDS_PER_SOLVE, grid::CRBA_OUT_PER_SOLVE);
+// end-effector kinematics: pose, gradient, Hessian (the `which` of ee_device)
+constexpr kernel_shape EE[3] = {outer(grid::EE_POS_SUGGESTED_THREADS, grid::EE_POS_LDS_PER_SOLVE, grid::EE_POS_OUT_PER_SOLVE),
+                                outer(grid::DEE_POS_SUGGESTED_THREADS, grid::DEE_POS_LDS_PER_SOLVE, grid::DEE_POS_OUT_PER_SOLVE),
+                                outer(grid::D2EE_POS_SUGGESTED_THREADS, grid::D2EE_POS_LDS_PER_SOLVE, grid::D2EE_POS_OUT_PER_SOLVE)};
+constexpr kernel_shape ROLLOUT = outer(grid::ROLLOUT_SUGGESTED_THREADS, grid::ROLLOUT_LDS_PER_SOLVE, grid::ROLLOUT_OUT_PER_SOLVE);
+constexpr kernel_shape ROLLOUT_LIN = outer(grid::ROLLOUT_LIN_SUGGESTED_THREADS, grid::ROLLOUT_LIN_LDS_PER_SOLVE, grid::ROLLOUT_LIN_OUT_PER_SOLVE);
+constexpr kernel_shape ROLLOUT_ADJ = outer(grid::ROLLOUT_ADJ_SUGGESTED_THREADS, grid::ROLLOUT_ADJ_LDS_PER_SOLVE, grid::ROLLOUT_ADJ_OUT_PER_SOLVE);
+#if GRID_HAS_IDSVA_SO
+// (the second-order kernels of 8-lane robots run 16-lane groups: namespace wide)
+constexpr kernel_shape IDSVA_SO{grid_so::IDSVA_SO_SUGGESTED_THREADS, grid_so::IDSVA_SO_MAX_SOLVES_PER_BLOCK, grid_so::IDSVA_SO_LDS_PER_SOLVE, grid_so::IDSVA_SO_STAGE_PER_SOLVE, grid_so::GRID_LANES_PER_SOLVE};
+constexpr kernel_shape FDSVA_SO{grid_so::FDSVA_SO_SUGGESTED_THREADS, grid_so::FDSVA_SO_MAX_SOLVES_PER_BLOCK, grid_so::FDSVA_SO_LDS_PER_SOLVE, grid_so::FDSVA_SO_STAGE_PER_SOLVE, grid_so::GRID_LANES_PER_SOLVE};
+#endif
+}  // namespace shape
+
 template <typename T>
-static int make_launch(const grid_handle *h, int num_timesteps, int default_threads, int max_groups, int lds_per_solve, int out_per_solve, launch_cfg *cfg,
-                       int lanes = grid::GRID_LANES_PER_SOLVE) {
-    int threads = h->threads > 0 ? h->threads : default_threads;
-    if (threads < lanes) threads = lanes;  // (the second-order kernels of 8-lane robots run 16-lane groups: namespace wide)
+static int make_launch(const grid_handle *h, int num_timesteps, const kernel_shape &k, launch_cfg *cfg) {
+    int threads = h->threads > 0 ? h->threads : k.threads;
+    if (threads < k.lanes) threads = k.lanes;  // (the second-order kernels of 8-lane robots run 16-lane groups: namespace wide)
     if (threads < grid::GRID_MIN_THREADS || threads > grid::GRID_MAX_THREADS)
         return fail_msg(hipErrorInvalidConfiguration, "threads per block out of range");
-    if (lanes == grid::GRID_LANES_PER_SOLVE) threads -= threads % grid::GRID_MIN_THREADS;  // (GRID_LANE_INTERLEAVE: blocks are whole 16-lane rows; the kernels retire the rest)
-    int gpb = threads / lanes;
-    if (gpb > max_groups) gpb = max_groups;  // (the kernels retire the lane groups beyond their cap)
-    const size_t per_group = (size_t)(lds_per_solve + out_per_solve) * sizeof(T);
+    if (k.lanes == grid::GRID_LANES_PER_SOLVE) threads -= threads % grid::GRID_MIN_THREADS;  // (GRID_LANE_INTERLEAVE: blocks are whole 16-lane rows; the kernels retire the rest)
+    int gpb = threads / k.lanes;
+    if (gpb > k.max_groups) gpb = k.max_groups;  // (the kernels retire the lane groups beyond their cap)
+    const size_t per_group = (size_t)(k.lds + k.out) * sizeof(T);
     if ((size_t)gpb * per_group > GRID_CU_LDS_BYTES) {
         // e.g. the 30-DoF robot in double precision: fewer solves per block than the block size suggests
         gpb = (int)(GRID_CU_LDS_BYTES / per_group);
         if (gpb < 1) return fail_msg(hipErrorInvalidConfiguration, "one solve of this robot does not fit the LDS of a CU in this precision");
-        threads = gpb * lanes;
+        threads = gpb * k.lanes;
     }
     int blocks = h->blocks > 0 ? h->blocks : (num_timesteps + gpb - 1) / gpb;
     if (blocks < 1) blocks = 1;
     cfg->grid = dim3(blocks, 1, 1);
     cfg->block = dim3(threads, 1, 1);
     cfg->lds = (size_t)gpb * per_group;
-    return 0;
-}
-template <typename T>
-static int general_launch(const grid_handle *h, int num_timesteps, launch_cfg *cfg) {
-    return make_launch<T>(h, num_timesteps, grid::SUGGESTED_THREADS, grid::GRID_MAX_SOLVES_PER_BLOCK, grid::GRID_LDS_PER_SOLVE, grid::GRID_OUT_PER_SOLVE, cfg);
-}
-
-// device entry points: required pointers must not be NULL and the stride must cover what the kernel loads per solve (a smaller or negative stride
-// would make the last solves read before / past the caller's buffer: a GPU memory fault instead of an error code)
-static int check_io(const void *in, int stride, int min_stride, const void *out, int num_timesteps) {
-    if (num_timesteps <= 0) return 0;
-    if (!in || !out) return fail_msg(hipErrorInvalidValue, "null input or output pointer");
-    if (stride < min_stride) {
-        snprintf(g_err, sizeof(g_err), "stride %d is smaller than the %d values the kernel reads per solve", stride, min_stride);
-        return (int)hipErrorInvalidValue;
-    }
     return 0;
 }
 
@@ -181,6 +197,19 @@ static int check_args(const grid_handle *h, int num_timesteps) {
     if (h->threads != 0 && (h->threads < grid::GRID_MIN_THREADS || h->threads > grid::GRID_MAX_THREADS)) {
         snprintf(g_err, sizeof(g_err), "threads per block must be in [%d, %d]", grid::GRID_MIN_THREADS, grid::GRID_MAX_THREADS);
         return (int)hipErrorInvalidConfiguration;
+    }
+    return 0;
+}
+
+// device entry points with one strided input and one output: check_args, then: required pointers must not be NULL and the stride must cover what the kernel loads per
+// solve (a smaller or negative stride would make the last solves read before / past the caller's buffer: a GPU memory fault instead of an error code)
+static int check_device_io(const grid_handle *h, const void *in, int stride, int min_stride, const void *out, int num_timesteps) {
+    const int rc = check_args(h, num_timesteps);
+    if (rc || num_timesteps == 0) return rc;
+    if (!in || !out) return fail_msg(hipErrorInvalidValue, "null input or output pointer");
+    if (stride < min_stride) {
+        snprintf(g_err, sizeof(g_err), "stride %d is smaller than the %d values the kernel reads per solve", stride, min_stride);
+        return (int)hipErrorInvalidValue;
     }
     return 0;
 }
@@ -227,133 +256,108 @@ static int ensure_typed(grid_handle *h) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------- device entry points
+// What every device entry point does between the checks of its own arguments (`checked`: what they returned) and its launch.  A failed check or N == 0 ends the
+// call with rc, before the device is switched and before anything is allocated.  Otherwise the handle's device is made current (and the caller's restored when
+// this object goes: it lives across the launch), the handle's state for T is allocated on first use and the launch geometry of the kernel is worked out.
+// ready: the caller launches; else it returns rc (grid_last_error is set where rc != 0).
 template <typename T>
-static int fd_grad_device(grid_handle *h, const T *d_q_qd_u, int stride, int N, T gravity, T *d_df_du, void *stream) {
-    int rc = check_args(h, N);
-    if (rc) return rc;
-    if ((rc = check_io(d_q_qd_u, stride, 3*(int)grid::NUM_JOINTS, d_df_du, N))) return rc;
-    if (N == 0) return 0;
-    GRID_ON_DEVICE(h);
-    if ((rc = ensure_typed<T>(h))) return rc;
-    launch_cfg c;
-    // this kernel has its own (smaller) LDS slice and suggested block size: FD_DU_LDS_PER_SOLVE, FD_DU_SUGGESTED_THREADS
-    if ((rc = make_launch<T>(h, N, grid::FD_DU_SUGGESTED_THREADS, grid::GRID_MAX_SOLVES_PER_BLOCK, grid::FD_DU_LDS_PER_SOLVE, grid::FD_DU_OUT_PER_SOLVE, &c))) return rc;
-    hipLaunchKernelGGL((grid::forward_dynamics_gradient_kernel<T>), c.grid, c.block, c.lds, (hipStream_t)stream, d_df_du, d_q_qd_u, stride,
-                       typed<T>(h).d_robotModel, gravity, N);
+struct device_launch : launch_cfg {
+    std::optional<device_guard> guard;
+    const grid::robotModel<T> *model = nullptr;
+    int rc;
+    bool ready = false;
+    device_launch(grid_handle *h, int N, const kernel_shape &k, int checked) : rc(checked) {
+        if (rc || N == 0) return;
+        guard.emplace(h->device);
+        rc = guard->err != hipSuccess ? fail(guard->err, "hipSetDevice(handle device)") : ensure_typed<T>(h);
+        if (!rc) rc = make_launch<T>(h, N, k, this);
+        if (!rc) model = typed<T>(h).d_robotModel;
+        ready = !rc;
+    }
+};
+// ... and after it
+static int launch_status() {
     GRID_TRY(hipGetLastError());
     return 0;
+}
+
+template <typename T>
+static int fd_grad_device(grid_handle *h, const T *d_q_qd_u, int stride, int N, T gravity, T *d_df_du, void *stream) {
+    device_launch<T> L(h, N, shape::FD_DU, check_device_io(h, d_q_qd_u, stride, 3*(int)grid::NUM_JOINTS, d_df_du, N));
+    if (!L.ready) return L.rc;
+    hipLaunchKernelGGL((grid::forward_dynamics_gradient_kernel<T>), L.grid, L.block, L.lds, (hipStream_t)stream, d_df_du, d_q_qd_u, stride, L.model, gravity, N);
+    return launch_status();
 }
 
 template <typename T>
 static int fd_grad_qdd_minv_device(grid_handle *h, const T *d_q_qd, int stride, const T *d_qdd, const T *d_Minv, int N, T gravity, T *d_df_du, void *stream) {
-    int rc = check_args(h, N);
-    if (rc) return rc;
-    if ((rc = check_io(d_q_qd, stride, 2*(int)grid::NUM_JOINTS, d_df_du, N))) return rc;
-    if (N > 0 && (!d_qdd || !d_Minv)) return fail_msg(hipErrorInvalidValue, "null qdd or Minv pointer");
-    if (N == 0) return 0;
-    GRID_ON_DEVICE(h);
-    if ((rc = ensure_typed<T>(h))) return rc;
-    launch_cfg c;
-    if ((rc = general_launch<T>(h, N, &c))) return rc;
-    hipLaunchKernelGGL((grid::forward_dynamics_gradient_kernel<T>), c.grid, c.block, c.lds, (hipStream_t)stream, d_df_du, d_q_qd, stride, d_qdd, d_Minv,
-                       typed<T>(h).d_robotModel, gravity, N);
-    GRID_TRY(hipGetLastError());
-    return 0;
+    int rc = check_device_io(h, d_q_qd, stride, 2*(int)grid::NUM_JOINTS, d_df_du, N);
+    if (!rc && N > 0 && (!d_qdd || !d_Minv)) rc = fail_msg(hipErrorInvalidValue, "null qdd or Minv pointer");
+    device_launch<T> L(h, N, shape::GENERAL, rc);
+    if (!L.ready) return L.rc;
+    hipLaunchKernelGGL((grid::forward_dynamics_gradient_kernel<T>), L.grid, L.block, L.lds, (hipStream_t)stream, d_df_du, d_q_qd, stride, d_qdd, d_Minv, L.model, gravity, N);
+    return launch_status();
 }
 
 template <typename T>
 static int id_device(grid_handle *h, const T *d_q_qd, int stride, const T *d_qdd, int N, T gravity, T *d_c, void *stream) {
-    int rc = check_args(h, N);
-    if (rc) return rc;
-    if ((rc = check_io(d_q_qd, stride, 2*(int)grid::NUM_JOINTS, d_c, N))) return rc;
-    if (N == 0) return 0;
-    GRID_ON_DEVICE(h);
-    if ((rc = ensure_typed<T>(h))) return rc;
-    launch_cfg c;
-    if ((rc = make_launch<T>(h, N, grid::ID_SUGGESTED_THREADS, grid::GRID_MAX_SOLVES_PER_BLOCK, grid::ID_LDS_PER_SOLVE, grid::ID_OUT_PER_SOLVE, &c))) return rc;
+    device_launch<T> L(h, N, shape::ID, check_device_io(h, d_q_qd, stride, 2*(int)grid::NUM_JOINTS, d_c, N));
+    if (!L.ready) return L.rc;
     if (d_qdd) {
-        hipLaunchKernelGGL((grid::inverse_dynamics_kernel<T>), c.grid, c.block, c.lds, (hipStream_t)stream, d_c, d_q_qd, stride, d_qdd, typed<T>(h).d_robotModel, gravity, N);
+        hipLaunchKernelGGL((grid::inverse_dynamics_kernel<T>), L.grid, L.block, L.lds, (hipStream_t)stream, d_c, d_q_qd, stride, d_qdd, L.model, gravity, N);
     } else {
-        hipLaunchKernelGGL((grid::inverse_dynamics_kernel<T>), c.grid, c.block, c.lds, (hipStream_t)stream, d_c, d_q_qd, stride, typed<T>(h).d_robotModel, gravity, N);
+        hipLaunchKernelGGL((grid::inverse_dynamics_kernel<T>), L.grid, L.block, L.lds, (hipStream_t)stream, d_c, d_q_qd, stride, L.model, gravity, N);
     }
-    GRID_TRY(hipGetLastError());
-    return 0;
+    return launch_status();
 }
 
 template <typename T>
 static int id_grad_device(grid_handle *h, const T *d_q_qd, int stride, const T *d_qdd, int N, T gravity, T *d_dc_du, void *stream) {
-    int rc = check_args(h, N);
-    if (rc) return rc;
-    if ((rc = check_io(d_q_qd, stride, 2*(int)grid::NUM_JOINTS, d_dc_du, N))) return rc;
-    if (N == 0) return 0;
-    GRID_ON_DEVICE(h);
-    if ((rc = ensure_typed<T>(h))) return rc;
-    launch_cfg c;
-    if ((rc = make_launch<T>(h, N, grid::ID_DU_SUGGESTED_THREADS, grid::GRID_MAX_SOLVES_PER_BLOCK, grid::ID_DU_LDS_PER_SOLVE, grid::ID_DU_OUT_PER_SOLVE, &c))) return rc;
+    device_launch<T> L(h, N, shape::ID_DU, check_device_io(h, d_q_qd, stride, 2*(int)grid::NUM_JOINTS, d_dc_du, N));
+    if (!L.ready) return L.rc;
     if (d_qdd) {
-        hipLaunchKernelGGL((grid::inverse_dynamics_gradient_kernel<T>), c.grid, c.block, c.lds, (hipStream_t)stream, d_dc_du, d_q_qd, stride, d_qdd,
-                           typed<T>(h).d_robotModel, gravity, N);
+        hipLaunchKernelGGL((grid::inverse_dynamics_gradient_kernel<T>), L.grid, L.block, L.lds, (hipStream_t)stream, d_dc_du, d_q_qd, stride, d_qdd, L.model, gravity, N);
     } else {
-        hipLaunchKernelGGL((grid::inverse_dynamics_gradient_kernel<T>), c.grid, c.block, c.lds, (hipStream_t)stream, d_dc_du, d_q_qd, stride,
-                           typed<T>(h).d_robotModel, gravity, N);
+        hipLaunchKernelGGL((grid::inverse_dynamics_gradient_kernel<T>), L.grid, L.block, L.lds, (hipStream_t)stream, d_dc_du, d_q_qd, stride, L.model, gravity, N);
     }
-    GRID_TRY(hipGetLastError());
-    return 0;
+    return launch_status();
 }
 
 template <typename T>
 static int minv_device(grid_handle *h, const T *d_q, int stride, int N, T *d_Minv, void *stream) {
-    int rc = check_args(h, N);
-    if (rc) return rc;
-    if ((rc = check_io(d_q, stride, 1*(int)grid::NUM_JOINTS, d_Minv, N))) return rc;
-    if (N == 0) return 0;
-    GRID_ON_DEVICE(h);
-    if ((rc = ensure_typed<T>(h))) return rc;
-    launch_cfg c;
-    if ((rc = make_launch<T>(h, N, grid::MINV_SUGGESTED_THREADS, grid::GRID_MAX_SOLVES_PER_BLOCK, grid::MINV_LDS_PER_SOLVE, grid::MINV_OUT_PER_SOLVE, &c))) return rc;
-    hipLaunchKernelGGL((grid::direct_minv_kernel<T>), c.grid, c.block, c.lds, (hipStream_t)stream, d_Minv, d_q, stride, typed<T>(h).d_robotModel, N);
-    GRID_TRY(hipGetLastError());
-    return 0;
+    device_launch<T> L(h, N, shape::MINV, check_device_io(h, d_q, stride, 1*(int)grid::NUM_JOINTS, d_Minv, N));
+    if (!L.ready) return L.rc;
+    hipLaunchKernelGGL((grid::direct_minv_kernel<T>), L.grid, L.block, L.lds, (hipStream_t)stream, d_Minv, d_q, stride, L.model, N);
+    return launch_status();
 }
 
 template <typename T>
 static int fd_device(grid_handle *h, const T *d_q_qd_u, int stride, int N, T gravity, T *d_qdd, void *stream, bool aba) {
-    int rc = check_args(h, N);
-    if (rc) return rc;
-    if ((rc = check_io(d_q_qd_u, stride, 3*(int)grid::NUM_JOINTS, d_qdd, N))) return rc;
-    if (N == 0) return 0;
-    GRID_ON_DEVICE(h);
-    if ((rc = ensure_typed<T>(h))) return rc;
-    launch_cfg c;
-    if ((rc = aba ? make_launch<T>(h, N, grid::ABA_SUGGESTED_THREADS, grid::GRID_MAX_SOLVES_PER_BLOCK, grid::ABA_LDS_PER_SOLVE, grid::ABA_OUT_PER_SOLVE, &c) : make_launch<T>(h, N, grid::FD_SUGGESTED_THREADS, grid::GRID_MAX_SOLVES_PER_BLOCK, grid::FD_LDS_PER_SOLVE, grid::FD_OUT_PER_SOLVE, &c))) return rc;
+    device_launch<T> L(h, N, aba ? shape::ABA : shape::FD, check_device_io(h, d_q_qd_u, stride, 3*(int)grid::NUM_JOINTS, d_qdd, N));
+    if (!L.ready) return L.rc;
     if (aba) {
-        hipLaunchKernelGGL((grid::aba_kernel<T>), c.grid, c.block, c.lds, (hipStream_t)stream, d_qdd, d_q_qd_u, stride, typed<T>(h).d_robotModel, gravity, N);
+        hipLaunchKernelGGL((grid::aba_kernel<T>), L.grid, L.block, L.lds, (hipStream_t)stream, d_qdd, d_q_qd_u, stride, L.model, gravity, N);
     } else {
-        hipLaunchKernelGGL((grid::forward_dynamics_kernel<T>), c.grid, c.block, c.lds, (hipStream_t)stream, d_qdd, d_q_qd_u, stride, typed<T>(h).d_robotModel, gravity, N);
+        hipLaunchKernelGGL((grid::forward_dynamics_kernel<T>), L.grid, L.block, L.lds, (hipStream_t)stream, d_qdd, d_q_qd_u, stride, L.model, gravity, N);
     }
-    GRID_TRY(hipGetLastError());
-    return 0;
+    return launch_status();
 }
 
 template <typename T>
 static int idsva_so_device(grid_handle *h, const T *d_q_qd_u, int stride, const T *d_qdd, int N, T gravity, T *d_idsva_so, void *stream) {
-    int rc = check_args(h, N);
-    if (rc) return rc;
-    if ((rc = check_io(d_q_qd_u, stride, 2*(int)grid::NUM_JOINTS, d_idsva_so, N))) return rc;
+    const int rc = check_device_io(h, d_q_qd_u, stride, 2*(int)grid::NUM_JOINTS, d_idsva_so, N);
 #if GRID_HAS_IDSVA_SO
-    if (N == 0) return 0;
-    GRID_ON_DEVICE(h);
-    if ((rc = ensure_typed<T>(h))) return rc;
-    launch_cfg c;
-    if ((rc = make_launch<T>(h, N, grid_so::IDSVA_SO_SUGGESTED_THREADS, grid_so::IDSVA_SO_MAX_SOLVES_PER_BLOCK, grid_so::IDSVA_SO_LDS_PER_SOLVE, grid_so::IDSVA_SO_STAGE_PER_SOLVE, &c, grid_so::GRID_LANES_PER_SOLVE))) return rc;
+    device_launch<T> L(h, N, shape::IDSVA_SO, rc);
+    if (!L.ready) return L.rc;
+    const grid_so::robotModel<T> *model = reinterpret_cast<const grid_so::robotModel<T> *>(L.model);
     if (d_qdd) {
-        hipLaunchKernelGGL((grid_so::idsva_so_kernel<T>), c.grid, c.block, c.lds, (hipStream_t)stream, d_idsva_so, d_q_qd_u, stride, d_qdd, reinterpret_cast<const grid_so::robotModel<T> *>(typed<T>(h).d_robotModel), gravity, N);
+        hipLaunchKernelGGL((grid_so::idsva_so_kernel<T>), L.grid, L.block, L.lds, (hipStream_t)stream, d_idsva_so, d_q_qd_u, stride, d_qdd, model, gravity, N);
     } else {
-        hipLaunchKernelGGL((grid_so::idsva_so_kernel<T>), c.grid, c.block, c.lds, (hipStream_t)stream, d_idsva_so, d_q_qd_u, stride, reinterpret_cast<const grid_so::robotModel<T> *>(typed<T>(h).d_robotModel), gravity, N);
+        hipLaunchKernelGGL((grid_so::idsva_so_kernel<T>), L.grid, L.block, L.lds, (hipStream_t)stream, d_idsva_so, d_q_qd_u, stride, model, gravity, N);
     }
-    GRID_TRY(hipGetLastError());
-    return 0;
+    return launch_status();
 #else
+    if (rc) return rc;
     (void)d_q_qd_u; (void)stride; (void)d_qdd; (void)gravity; (void)d_idsva_so; (void)stream;
     return fail_msg(hipErrorNotSupported, "idsva_so is not emitted for this library's robot (see GRID_HAS_IDSVA_SO in the generated header)");
 #endif
@@ -361,15 +365,11 @@ static int idsva_so_device(grid_handle *h, const T *d_q_qd_u, int stride, const 
 
 template <typename T>
 static int fdsva_so_device(grid_handle *h, const T *d_q_qd_u, int stride, int N, T gravity, T *d_df2, void *stream) {
-    int rc = check_args(h, N);
-    if (rc) return rc;
-    if ((rc = check_io(d_q_qd_u, stride, 3*(int)grid::NUM_JOINTS, d_df2, N))) return rc;
+    const int rc = check_device_io(h, d_q_qd_u, stride, 3*(int)grid::NUM_JOINTS, d_df2, N);
 #if GRID_HAS_IDSVA_SO
-    if (N == 0) return 0;
-    GRID_ON_DEVICE(h);
-    if ((rc = ensure_typed<T>(h))) return rc;
-    launch_cfg c;
-    if ((rc = make_launch<T>(h, N, grid_so::FDSVA_SO_SUGGESTED_THREADS, grid_so::FDSVA_SO_MAX_SOLVES_PER_BLOCK, grid_so::FDSVA_SO_LDS_PER_SOLVE, grid_so::FDSVA_SO_STAGE_PER_SOLVE, &c, grid_so::GRID_LANES_PER_SOLVE))) return rc;
+    device_launch<T> L(h, N, shape::FDSVA_SO, rc);
+    if (!L.ready) return L.rc;
+    const grid_so::robotModel<T> *model = reinterpret_cast<const grid_so::robotModel<T> *>(L.model);
 #if GRID_SO_DIRECT
     // the idsva_so tensors of a solve do not fit LDS: the kernel keeps them in the handle's d_idsva_so buffer
     if (N > so_capacity<T>(h)) return fail_msg(hipErrorInvalidValue, "num_timesteps exceeds the handle's second-order workspace (grid_second_order_capacity)");
@@ -379,24 +379,24 @@ static int fdsva_so_device(grid_handle *h, const T *d_q_qd_u, int stride, int N,
         if (h->so_pending) GRID_TRY(hipStreamWaitEvent((hipStream_t)stream, h->so_done, 0));  // (the previous launch may be on another stream)
 #if GRID_SO_SPLIT
         // two kernels: gradient, M^-1 and the tensors by lane groups into the handle's buffers, then the contraction with one block per solve
-        hipLaunchKernelGGL((grid_so::fdsva_so_prepare_kernel<T>), c.grid, c.block, c.lds, (hipStream_t)stream, typed<T>(h).hd_data->d_idsva_so, typed<T>(h).hd_data->d_df_du,
-                           typed<T>(h).hd_data->d_Minv, d_q_qd_u, stride, reinterpret_cast<const grid_so::robotModel<T> *>(typed<T>(h).d_robotModel), gravity, N);
+        hipLaunchKernelGGL((grid_so::fdsva_so_prepare_kernel<T>), L.grid, L.block, L.lds, (hipStream_t)stream, typed<T>(h).hd_data->d_idsva_so, typed<T>(h).hd_data->d_df_du,
+                           typed<T>(h).hd_data->d_Minv, d_q_qd_u, stride, model, gravity, N);
         GRID_TRY(hipGetLastError());
         hipLaunchKernelGGL((grid_so::fdsva_so_contract_kernel<T>), dim3(N < 4096 ? N : 4096), dim3(grid_so::FDSVA_SO_CONTRACT_THREADS), (size_t)grid_so::FDSVA_SO_CONTRACT_LDS * sizeof(T),
                            (hipStream_t)stream, d_df2, typed<T>(h).hd_data->d_idsva_so, typed<T>(h).hd_data->d_df_du, typed<T>(h).hd_data->d_Minv, N);
 #else
-        hipLaunchKernelGGL((grid_so::fdsva_so_kernel<T>), c.grid, c.block, c.lds, (hipStream_t)stream, d_df2, typed<T>(h).hd_data->d_idsva_so, d_q_qd_u, stride, reinterpret_cast<const grid_so::robotModel<T> *>(typed<T>(h).d_robotModel), gravity, N);
+        hipLaunchKernelGGL((grid_so::fdsva_so_kernel<T>), L.grid, L.block, L.lds, (hipStream_t)stream, d_df2, typed<T>(h).hd_data->d_idsva_so, d_q_qd_u, stride, model, gravity, N);
 #endif
         GRID_TRY(hipGetLastError());
         GRID_TRY(hipEventRecord(h->so_done, (hipStream_t)stream));
         h->so_pending = true;
     }
 #else
-    hipLaunchKernelGGL((grid_so::fdsva_so_kernel<T>), c.grid, c.block, c.lds, (hipStream_t)stream, d_df2, d_q_qd_u, stride, reinterpret_cast<const grid_so::robotModel<T> *>(typed<T>(h).d_robotModel), gravity, N);
+    hipLaunchKernelGGL((grid_so::fdsva_so_kernel<T>), L.grid, L.block, L.lds, (hipStream_t)stream, d_df2, d_q_qd_u, stride, model, gravity, N);
 #endif
-    GRID_TRY(hipGetLastError());
-    return 0;
+    return launch_status();
 #else
+    if (rc) return rc;
     (void)d_q_qd_u; (void)stride; (void)gravity; (void)d_df2; (void)stream;
     return fail_msg(hipErrorNotSupported, "fdsva_so is not emitted for this library's robot (see GRID_HAS_IDSVA_SO in the generated header)");
 #endif
@@ -582,31 +582,21 @@ static const size_t EE_REC[3] = {(size_t)6 * grid::NUM_EES, (size_t)6 * grid::NU
 
 template <typename T>
 static int ee_device(grid_handle *h, const T *d_q, int stride, int N, T *d_out, T *d_dee, void *stream, int which) {
-    int rc = check_args(h, N);
-    if (rc) return rc;
-    if ((rc = check_io(d_q, stride, (int)grid::NUM_JOINTS, d_out, N))) return rc;
-    if (N == 0) return 0;
-    GRID_ON_DEVICE(h);
-    if ((rc = ensure_typed<T>(h))) return rc;
-    launch_cfg c;
-    const grid::robotModel<T> *rm = typed<T>(h).d_robotModel;
+    device_launch<T> L(h, N, shape::EE[which], check_device_io(h, d_q, stride, (int)grid::NUM_JOINTS, d_out, N));
+    if (!L.ready) return L.rc;
     if (which == 0) {
-        if ((rc = make_launch<T>(h, N, grid::EE_POS_SUGGESTED_THREADS, grid::GRID_MAX_SOLVES_PER_BLOCK, grid::EE_POS_LDS_PER_SOLVE, grid::EE_POS_OUT_PER_SOLVE, &c))) return rc;
-        hipLaunchKernelGGL((grid::end_effector_pose_kernel<T>), c.grid, c.block, c.lds, (hipStream_t)stream, d_out, d_q, stride, rm, N);
+        hipLaunchKernelGGL((grid::end_effector_pose_kernel<T>), L.grid, L.block, L.lds, (hipStream_t)stream, d_out, d_q, stride, L.model, N);
     } else if (which == 1) {
-        if ((rc = make_launch<T>(h, N, grid::DEE_POS_SUGGESTED_THREADS, grid::GRID_MAX_SOLVES_PER_BLOCK, grid::DEE_POS_LDS_PER_SOLVE, grid::DEE_POS_OUT_PER_SOLVE, &c))) return rc;
-        hipLaunchKernelGGL((grid::end_effector_pose_gradient_kernel<T>), c.grid, c.block, c.lds, (hipStream_t)stream, d_out, d_q, stride, rm, N);
+        hipLaunchKernelGGL((grid::end_effector_pose_gradient_kernel<T>), L.grid, L.block, L.lds, (hipStream_t)stream, d_out, d_q, stride, L.model, N);
     } else {
-        if ((rc = make_launch<T>(h, N, grid::D2EE_POS_SUGGESTED_THREADS, grid::GRID_MAX_SOLVES_PER_BLOCK, grid::D2EE_POS_LDS_PER_SOLVE, grid::D2EE_POS_OUT_PER_SOLVE, &c))) return rc;
-        hipLaunchKernelGGL((grid::end_effector_pose_gradient_hessian_kernel<T>), c.grid, c.block, c.lds, (hipStream_t)stream, d_out, d_dee, d_q, stride, rm, N);
+        hipLaunchKernelGGL((grid::end_effector_pose_gradient_hessian_kernel<T>), L.grid, L.block, L.lds, (hipStream_t)stream, d_out, d_dee, d_q, stride, L.model, N);
     }
-    GRID_TRY(hipGetLastError());
-    return 0;
+    return launch_status();
 }
 
 // grows one device staging buffer to at least `count` elements (the caller holds alloc_lock)
 template <typename T>
-static int ee_grow(T **buf, size_t *cap, size_t count) {
+static int grow_staging(T **buf, size_t *cap, size_t count) {
     if (*cap >= count) return 0;
     if (*buf) GRID_TRY(hipFree(*buf));
     *buf = nullptr;
@@ -637,9 +627,9 @@ static int ee_host(grid_handle *h, const T *h_q, int stride, int N, T *h_out, T 
     ee_stage<T> &st = ee_staging<T>(h);
     {
         std::lock_guard<std::mutex> lock(h->alloc_lock);
-        if ((rc = ee_grow<T>(&st.d_q, &st.q_cap, (size_t)stride * chunk))) return rc;
-        if ((rc = ee_grow<T>(&st.d_out, &st.out_cap, rec * chunk))) return rc;
-        if (dee && (rc = ee_grow<T>(&st.d_dee, &st.dee_cap, grad * chunk))) return rc;
+        if ((rc = grow_staging<T>(&st.d_q, &st.q_cap, (size_t)stride * chunk))) return rc;
+        if ((rc = grow_staging<T>(&st.d_out, &st.out_cap, rec * chunk))) return rc;
+        if (dee && (rc = grow_staging<T>(&st.d_dee, &st.dee_cap, grad * chunk))) return rc;
     }
     hipStream_t s = h->streams[0];
     for (size_t k0 = 0; k0 < (size_t)N; k0 += chunk) {
@@ -664,17 +654,10 @@ static void ee_release(ee_stage<T> &st) {
 // ---------------------------------------------------------------------------------------------------------------- joint-space inertia matrix
 template <typename T>
 static int crba_device(grid_handle *h, const T *d_q, int stride, int N, T *d_M, void *stream) {
-    int rc = check_args(h, N);
-    if (rc) return rc;
-    if ((rc = check_io(d_q, stride, (int)grid::NUM_JOINTS, d_M, N))) return rc;
-    if (N == 0) return 0;
-    GRID_ON_DEVICE(h);
-    if ((rc = ensure_typed<T>(h))) return rc;
-    launch_cfg c;
-    if ((rc = make_launch<T>(h, N, grid::CRBA_SUGGESTED_THREADS, grid::GRID_MAX_SOLVES_PER_BLOCK, grid::CRBA_LDS_PER_SOLVE, grid::CRBA_OUT_PER_SOLVE, &c))) return rc;
-    hipLaunchKernelGGL((grid::crba_kernel<T>), c.grid, c.block, c.lds, (hipStream_t)stream, d_M, d_q, stride, typed<T>(h).d_robotModel, (T)0, N);
-    GRID_TRY(hipGetLastError());
-    return 0;
+    device_launch<T> L(h, N, shape::CRBA, check_device_io(h, d_q, stride, (int)grid::NUM_JOINTS, d_M, N));
+    if (!L.ready) return L.rc;
+    hipLaunchKernelGGL((grid::crba_kernel<T>), L.grid, L.block, L.lds, (hipStream_t)stream, d_M, d_q, stride, L.model, (T)0, N);
+    return launch_status();
 }
 
 // Host buffers in, host buffers out, synchronous.  The output is staged in the handle's own hd_data->d_M (null after init_gridData, allocated here on
@@ -692,7 +675,7 @@ static int crba_host(grid_handle *h, const T *h_q, int stride, int N, T *h_M) {
     grid::gridData<T> *d = typed<T>(h).hd_data;
     {
         std::lock_guard<std::mutex> lock(h->alloc_lock);
-        if ((rc = ee_grow<T>(&d->d_M, &typed<T>(h).M_cap, n * n * (size_t)N))) return rc;
+        if ((rc = grow_staging<T>(&d->d_M, &typed<T>(h).M_cap, n * n * (size_t)N))) return rc;
     }
     hipStream_t s = h->streams[0];
     GRID_H2D(d->d_q_qd_u, h_q, (size_t)stride * N);
@@ -705,7 +688,19 @@ static int crba_host(grid_handle *h, const T *h_q, int stride, int N, T *h_M) {
 // ---------------------------------------------------------------------------------------------------------------- fused rollout
 // u: element (t, k, j) at d_u[t*stride_u_step + k*stride_u_solve + j].  Every solve's row must lie inside its step and the steps must not overlap
 // (a smaller or negative stride would read before / past the caller's buffer); stride_u_solve == 0 is the one legal alias: one sequence for all solves.
-static int check_rollout_strides(int stride_x0, long stride_u_step, int stride_u_solve, int N, int num_steps) {
+static long rollout_u_span(int stride_u_solve, int N) {  // what one step of the control touches
+    const long n = grid::NUM_JOINTS;
+    return stride_u_solve == 0 ? n : (long)(N - 1) * stride_u_solve + n;
+}
+
+// The checks every rollout entry point makes after check_args / host_prologue.  have_inputs, have_outputs: the caller's own null tests, the texts what it says
+// where they fail.  N == 0 is legal whatever the pointers are: 0 is returned before they are looked at, and the caller returns.
+static int check_rollout_call(int N, int num_steps, bool have_inputs, const char *no_inputs, bool have_outputs, const char *no_outputs, int stride_x0, long stride_u_step,
+                              int stride_u_solve) {
+    if (num_steps < 0) return fail_msg(hipErrorInvalidValue, "negative num_steps");
+    if (N == 0) return 0;
+    if (!have_inputs) return fail_msg(hipErrorInvalidValue, no_inputs);
+    if (!have_outputs) return fail_msg(hipErrorInvalidValue, no_outputs);
     const int n = (int)grid::NUM_JOINTS;
     if (stride_x0 < 2 * n) {
         snprintf(g_err, sizeof(g_err), "stride_x0 %d is smaller than the %d values [q | qd] the kernel reads per solve", stride_x0, 2 * n);
@@ -715,7 +710,7 @@ static int check_rollout_strides(int stride_x0, long stride_u_step, int stride_u
         snprintf(g_err, sizeof(g_err), "stride_u_solve %d must be 0 (one control sequence for all solves) or at least the %d controls of a solve", stride_u_solve, n);
         return (int)hipErrorInvalidValue;
     }
-    const long span = stride_u_solve == 0 ? (long)n : (long)(N - 1) * stride_u_solve + n;  // what one step touches
+    const long span = rollout_u_span(stride_u_solve, N);
     if (span > (long)INT_MAX) return fail_msg(hipErrorInvalidValue, "stride_u_solve * num_solves exceeds the 32-bit offsets the kernel uses inside one step");
     if (num_steps > 1 && stride_u_step < span) {
         snprintf(g_err, sizeof(g_err), "stride_u_step %ld is smaller than the %ld values one step of the control spans", stride_u_step, span);
@@ -724,24 +719,45 @@ static int check_rollout_strides(int stride_x0, long stride_u_step, int stride_u
     return 0;
 }
 
+// elements of the records the host entry points stage: the control as the caller laid it out ((num_steps - 1) whole steps and the span of the last one), one
+// (N, 2n) row of states, the num_steps + 1 rows of a trajectory
+struct rollout_counts {
+    size_t u, row, traj;
+};
+static rollout_counts rollout_extent(long stride_u_step, int stride_u_solve, int N, int num_steps) {
+    rollout_counts e;
+    e.u = num_steps > 0 ? (size_t)(num_steps - 1) * (size_t)stride_u_step + (size_t)rollout_u_span(stride_u_solve, N) : 0;
+    e.row = 2 * (size_t)grid::NUM_JOINTS * (size_t)N;
+    e.traj = e.row * ((size_t)num_steps + 1);
+    return e;
+}
+
+// the states of a forward rollout inside the handle's d_x_traj: the trajectory where it is asked for, xT behind it (alone: at the front)
+struct rollout_x_layout {
+    size_t count, xT_offset;
+    rollout_x_layout(const rollout_counts &e, bool traj, bool xT) : count(traj ? e.traj + (xT ? e.row : 0) : e.row), xT_offset(traj ? e.traj : 0) {}
+};
+
+// No staged record of a host call may exceed GRID_ROLLOUT_LIN_HOST_CAP_BYTES: such a call is refused before anything is allocated or copied.
+static int check_rollout_staging(const char *entry, int N, int num_steps, std::initializer_list<size_t> counts, size_t elem_bytes) {
+    const size_t largest = std::max(counts);
+    if (largest <= GRID_ROLLOUT_LIN_HOST_CAP_BYTES / elem_bytes) return 0;
+    snprintf(g_err, sizeof(g_err), "%s host staging capacity exceeded: %d solves x %d steps need %zu bytes for the largest record, the cap is %zu "
+             "(split the horizon or use the device entry point)", entry, N, num_steps, largest * elem_bytes, (size_t)GRID_ROLLOUT_LIN_HOST_CAP_BYTES);
+    return (int)hipErrorInvalidValue;
+}
+
 template <typename T>
 static int rollout_device(grid_handle *h, const T *d_x0, int stride_x0, const T *d_u, long stride_u_step, int stride_u_solve, int N, int num_steps, T dt, T gravity,
                           T *d_traj, T *d_xT, void *stream) {
     int rc = check_args(h, N);
-    if (rc) return rc;
-    if (num_steps < 0) return fail_msg(hipErrorInvalidValue, "negative num_steps");
-    if (N == 0) return 0;
-    if (!d_x0 || (num_steps > 0 && !d_u)) return fail_msg(hipErrorInvalidValue, "null input pointer");
-    if (!d_traj && !d_xT) return fail_msg(hipErrorInvalidValue, "null output pointers: at least one of traj and xT must be given");
-    if ((rc = check_rollout_strides(stride_x0, stride_u_step, stride_u_solve, N, num_steps))) return rc;
-    GRID_ON_DEVICE(h);
-    if ((rc = ensure_typed<T>(h))) return rc;
-    launch_cfg c;
-    if ((rc = make_launch<T>(h, N, grid::ROLLOUT_SUGGESTED_THREADS, grid::GRID_MAX_SOLVES_PER_BLOCK, grid::ROLLOUT_LDS_PER_SOLVE, grid::ROLLOUT_OUT_PER_SOLVE, &c))) return rc;
-    hipLaunchKernelGGL((grid::rollout_kernel<T>), c.grid, c.block, c.lds, (hipStream_t)stream, d_traj, d_xT, d_x0, stride_x0, d_u, stride_u_step, stride_u_solve,
-                       typed<T>(h).d_robotModel, dt, gravity, N, num_steps);
-    GRID_TRY(hipGetLastError());
-    return 0;
+    if (!rc) rc = check_rollout_call(N, num_steps, d_x0 && (num_steps == 0 || d_u), "null input pointer", d_traj || d_xT,
+                                     "null output pointers: at least one of traj and xT must be given", stride_x0, stride_u_step, stride_u_solve);
+    device_launch<T> L(h, N, shape::ROLLOUT, rc);
+    if (!L.ready) return L.rc;
+    hipLaunchKernelGGL((grid::rollout_kernel<T>), L.grid, L.block, L.lds, (hipStream_t)stream, d_traj, d_xT, d_x0, stride_x0, d_u, stride_u_step, stride_u_solve,
+                       L.model, dt, gravity, N, num_steps);
+    return launch_status();
 }
 
 // Host buffers in, host buffers out, synchronous.  x0 passes through the handle's d_q_qd_u; u and traj / xT do not fit the handle's 3n-per-solve buffers:
@@ -750,35 +766,27 @@ template <typename T>
 static int rollout_host(grid_handle *h, const T *h_x0, int stride_x0, const T *h_u, long stride_u_step, int stride_u_solve, int N, int num_steps, T dt, T gravity,
                         T *h_traj, T *h_xT) {
     int rc = host_prologue<T>(h, N);
-    if (rc) return rc;
-    if (num_steps < 0) return fail_msg(hipErrorInvalidValue, "negative num_steps");
-    if (N == 0) return 0;
-    if (!h_x0 || (num_steps > 0 && !h_u)) return fail_msg(hipErrorInvalidValue, "null input pointer");
-    if (!h_traj && !h_xT) return fail_msg(hipErrorInvalidValue, "null output pointers: at least one of traj and xT must be given");
-    if ((rc = check_rollout_strides(stride_x0, stride_u_step, stride_u_solve, N, num_steps))) return rc;
-    const size_t n = grid::NUM_JOINTS;
-    if (stride_x0 > 3 * (int)n) return fail_msg(hipErrorInvalidValue, "stride_x0 must be in [2n, 3n] for host buffers");
+    if (!rc) rc = check_rollout_call(N, num_steps, h_x0 && (num_steps == 0 || h_u), "null input pointer", h_traj || h_xT,
+                                     "null output pointers: at least one of traj and xT must be given", stride_x0, stride_u_step, stride_u_solve);
+    if (rc || N == 0) return rc;
+    if (stride_x0 > 3 * (int)grid::NUM_JOINTS) return fail_msg(hipErrorInvalidValue, "stride_x0 must be in [2n, 3n] for host buffers");
     GRID_ON_DEVICE(h);
     if ((rc = ensure_typed<T>(h))) return rc;
     grid::gridData<T> *d = typed<T>(h).hd_data;
-    // the control as the caller laid it out: (num_steps - 1) whole steps and the span of the last one
-    const size_t u_span = stride_u_solve == 0 ? n : (size_t)(N - 1) * stride_u_solve + n;
-    const size_t u_count = num_steps > 0 ? (size_t)(num_steps - 1) * (size_t)stride_u_step + u_span : 0;
-    const size_t row = 2 * n * (size_t)N;
-    const size_t x_count = h_traj ? row * ((size_t)num_steps + 1) + (h_xT ? row : 0) : row;
+    const rollout_counts e = rollout_extent(stride_u_step, stride_u_solve, N, num_steps);
+    const rollout_x_layout x(e, h_traj, h_xT);
     {
         std::lock_guard<std::mutex> lock(h->alloc_lock);
-        if ((rc = ee_grow<T>(&d->d_u_traj, &typed<T>(h).u_traj_cap, u_count > 0 ? u_count : 1))) return rc;
-        if ((rc = ee_grow<T>(&d->d_x_traj, &typed<T>(h).x_traj_cap, x_count))) return rc;
+        if ((rc = grow_staging<T>(&d->d_u_traj, &typed<T>(h).u_traj_cap, e.u > 0 ? e.u : 1))) return rc;
+        if ((rc = grow_staging<T>(&d->d_x_traj, &typed<T>(h).x_traj_cap, x.count))) return rc;
     }
-    T *d_traj = h_traj ? d->d_x_traj : nullptr;
-    T *d_xT = h_xT ? (h_traj ? d->d_x_traj + row * ((size_t)num_steps + 1) : d->d_x_traj) : nullptr;
+    T *d_traj = h_traj ? d->d_x_traj : nullptr, *d_xT = h_xT ? d->d_x_traj + x.xT_offset : nullptr;
     hipStream_t s = h->streams[0];
     GRID_H2D(d->d_q_qd_u, h_x0, (size_t)stride_x0 * N);
-    if (u_count > 0) GRID_H2D(d->d_u_traj, h_u, u_count);
+    if (e.u > 0) GRID_H2D(d->d_u_traj, h_u, e.u);
     if ((rc = rollout_device<T>(h, d->d_q_qd_u, stride_x0, d->d_u_traj, stride_u_step, stride_u_solve, N, num_steps, dt, gravity, d_traj, d_xT, (void *)s))) return rc;
-    if (h_traj) GRID_D2H(h_traj, d_traj, row * ((size_t)num_steps + 1));
-    if (h_xT) GRID_D2H(h_xT, d_xT, row);
+    if (h_traj) GRID_D2H(h_traj, d_traj, e.traj);
+    if (h_xT) GRID_D2H(h_xT, d_xT, e.row);
     GRID_TRY(hipStreamSynchronize(s));
     return 0;
 }
@@ -789,72 +797,51 @@ template <typename T>
 static int rollout_linearized_device(grid_handle *h, const T *d_x0, int stride_x0, const T *d_u, long stride_u_step, int stride_u_solve, int N, int num_steps, T dt, T gravity,
                                      T *d_traj, T *d_xT, T *d_fx, T *d_fu, void *stream) {
     int rc = check_args(h, N);
-    if (rc) return rc;
-    if (num_steps < 0) return fail_msg(hipErrorInvalidValue, "negative num_steps");
-    if (N == 0) return 0;
-    if (!d_x0 || (num_steps > 0 && !d_u)) return fail_msg(hipErrorInvalidValue, "null input pointer");
-    if (!d_traj && !d_xT && !d_fx && !d_fu) return fail_msg(hipErrorInvalidValue, "null output pointers: at least one of traj, xT, fx and fu must be given");
-    if ((rc = check_rollout_strides(stride_x0, stride_u_step, stride_u_solve, N, num_steps))) return rc;
-    if (num_steps == 0 && !d_traj && !d_xT) return 0;  // (no step: no Jacobian is written)
-    GRID_ON_DEVICE(h);
-    if ((rc = ensure_typed<T>(h))) return rc;
-    launch_cfg c;
-    if ((rc = make_launch<T>(h, N, grid::ROLLOUT_LIN_SUGGESTED_THREADS, grid::GRID_MAX_SOLVES_PER_BLOCK, grid::ROLLOUT_LIN_LDS_PER_SOLVE, grid::ROLLOUT_LIN_OUT_PER_SOLVE, &c))) return rc;
-    hipLaunchKernelGGL((grid::rollout_linearized_kernel<T>), c.grid, c.block, c.lds, (hipStream_t)stream, d_traj, d_xT, d_fx, d_fu, d_x0, stride_x0, d_u, stride_u_step,
-                       stride_u_solve, typed<T>(h).d_robotModel, dt, gravity, N, num_steps);
-    GRID_TRY(hipGetLastError());
-    return 0;
+    if (!rc) rc = check_rollout_call(N, num_steps, d_x0 && (num_steps == 0 || d_u), "null input pointer", d_traj || d_xT || d_fx || d_fu,
+                                     "null output pointers: at least one of traj, xT, fx and fu must be given", stride_x0, stride_u_step, stride_u_solve);
+    if (!rc && num_steps == 0 && !d_traj && !d_xT) return 0;  // (no step: no Jacobian is written)
+    device_launch<T> L(h, N, shape::ROLLOUT_LIN, rc);
+    if (!L.ready) return L.rc;
+    hipLaunchKernelGGL((grid::rollout_linearized_kernel<T>), L.grid, L.block, L.lds, (hipStream_t)stream, d_traj, d_xT, d_fx, d_fu, d_x0, stride_x0, d_u, stride_u_step,
+                       stride_u_solve, L.model, dt, gravity, N, num_steps);
+    return launch_status();
 }
 
-// Host buffers in, host buffers out, synchronous.  x0 passes through the handle's d_q_qd_u, u and traj / xT through d_u_traj / d_x_traj like rollout_host, the
-// Jacobians through hd_data->d_fx_traj / d_fu_traj (null after init_gridData, allocated here on first use, grown by longer calls, freed by close_grid).
-// No staged output may exceed GRID_ROLLOUT_LIN_HOST_CAP_BYTES: such a call is refused before anything is allocated or copied.
+// Host buffers in, host buffers out, synchronous.  x0, u and traj / xT as in rollout_host, the Jacobians through hd_data->d_fx_traj / d_fu_traj (same rules).
+// Subject to check_rollout_staging.
 template <typename T>
 static int rollout_linearized_host(grid_handle *h, const T *h_x0, int stride_x0, const T *h_u, long stride_u_step, int stride_u_solve, int N, int num_steps, T dt, T gravity,
                                    T *h_traj, T *h_xT, T *h_fx, T *h_fu) {
     int rc = host_prologue<T>(h, N);
-    if (rc) return rc;
-    if (num_steps < 0) return fail_msg(hipErrorInvalidValue, "negative num_steps");
-    if (N == 0) return 0;
-    if (!h_x0 || (num_steps > 0 && !h_u)) return fail_msg(hipErrorInvalidValue, "null input pointer");
-    if (!h_traj && !h_xT && !h_fx && !h_fu) return fail_msg(hipErrorInvalidValue, "null output pointers: at least one of traj, xT, fx and fu must be given");
-    if ((rc = check_rollout_strides(stride_x0, stride_u_step, stride_u_solve, N, num_steps))) return rc;
+    if (!rc) rc = check_rollout_call(N, num_steps, h_x0 && (num_steps == 0 || h_u), "null input pointer", h_traj || h_xT || h_fx || h_fu,
+                                     "null output pointers: at least one of traj, xT, fx and fu must be given", stride_x0, stride_u_step, stride_u_solve);
+    if (rc || N == 0) return rc;
     const size_t n = grid::NUM_JOINTS;
     if (stride_x0 > 3 * (int)n) return fail_msg(hipErrorInvalidValue, "stride_x0 must be in [2n, 3n] for host buffers");
-    const size_t u_span = stride_u_solve == 0 ? n : (size_t)(N - 1) * stride_u_solve + n;
-    const size_t u_count = num_steps > 0 ? (size_t)(num_steps - 1) * (size_t)stride_u_step + u_span : 0;
-    const size_t row = 2 * n * (size_t)N;
-    const size_t x_count = h_traj ? row * ((size_t)num_steps + 1) + (h_xT ? row : 0) : row;
+    const rollout_counts e = rollout_extent(stride_u_step, stride_u_solve, N, num_steps);
+    const rollout_x_layout x(e, h_traj, h_xT);
     const size_t fx_count = h_fx ? 2 * n * n * (size_t)N * (size_t)num_steps : 0;
     const size_t fu_count = h_fu ? n * n * (size_t)N * (size_t)num_steps : 0;
-    const size_t cap = GRID_ROLLOUT_LIN_HOST_CAP_BYTES / sizeof(T);
-    if (fx_count > cap || fu_count > cap || x_count > cap || u_count > cap) {
-        snprintf(g_err, sizeof(g_err), "rollout_linearized host staging capacity exceeded: %d solves x %d steps need %zu bytes for the largest record, the cap is %zu "
-                 "(split the horizon or use the device entry point)", N, num_steps,
-                 (fx_count > x_count ? (fx_count > u_count ? fx_count : u_count) : (x_count > u_count ? (x_count > fu_count ? x_count : fu_count) : u_count)) * sizeof(T),
-                 (size_t)GRID_ROLLOUT_LIN_HOST_CAP_BYTES);
-        return (int)hipErrorInvalidValue;
-    }
+    if ((rc = check_rollout_staging("rollout_linearized", N, num_steps, {fx_count, fu_count, x.count, e.u}, sizeof(T)))) return rc;
     GRID_ON_DEVICE(h);
     if ((rc = ensure_typed<T>(h))) return rc;
     grid::gridData<T> *d = typed<T>(h).hd_data;
     {
         std::lock_guard<std::mutex> lock(h->alloc_lock);
-        if ((rc = ee_grow<T>(&d->d_u_traj, &typed<T>(h).u_traj_cap, u_count > 0 ? u_count : 1))) return rc;
-        if ((rc = ee_grow<T>(&d->d_x_traj, &typed<T>(h).x_traj_cap, x_count))) return rc;
-        if (fx_count > 0 && (rc = ee_grow<T>(&d->d_fx_traj, &typed<T>(h).fx_traj_cap, fx_count))) return rc;
-        if (fu_count > 0 && (rc = ee_grow<T>(&d->d_fu_traj, &typed<T>(h).fu_traj_cap, fu_count))) return rc;
+        if ((rc = grow_staging<T>(&d->d_u_traj, &typed<T>(h).u_traj_cap, e.u > 0 ? e.u : 1))) return rc;
+        if ((rc = grow_staging<T>(&d->d_x_traj, &typed<T>(h).x_traj_cap, x.count))) return rc;
+        if (fx_count > 0 && (rc = grow_staging<T>(&d->d_fx_traj, &typed<T>(h).fx_traj_cap, fx_count))) return rc;
+        if (fu_count > 0 && (rc = grow_staging<T>(&d->d_fu_traj, &typed<T>(h).fu_traj_cap, fu_count))) return rc;
     }
-    T *d_traj = h_traj ? d->d_x_traj : nullptr;
-    T *d_xT = h_xT ? (h_traj ? d->d_x_traj + row * ((size_t)num_steps + 1) : d->d_x_traj) : nullptr;
+    T *d_traj = h_traj ? d->d_x_traj : nullptr, *d_xT = h_xT ? d->d_x_traj + x.xT_offset : nullptr;
     T *d_fx = fx_count > 0 ? d->d_fx_traj : nullptr, *d_fu = fu_count > 0 ? d->d_fu_traj : nullptr;
     if (!d_traj && !d_xT && !d_fx && !d_fu) return 0;  // (num_steps == 0 and Jacobians only: there is nothing to write)
     hipStream_t s = h->streams[0];
     GRID_H2D(d->d_q_qd_u, h_x0, (size_t)stride_x0 * N);
-    if (u_count > 0) GRID_H2D(d->d_u_traj, h_u, u_count);
+    if (e.u > 0) GRID_H2D(d->d_u_traj, h_u, e.u);
     if ((rc = rollout_linearized_device<T>(h, d->d_q_qd_u, stride_x0, d->d_u_traj, stride_u_step, stride_u_solve, N, num_steps, dt, gravity, d_traj, d_xT, d_fx, d_fu, (void *)s))) return rc;
-    if (h_traj) GRID_D2H(h_traj, d_traj, row * ((size_t)num_steps + 1));
-    if (h_xT) GRID_D2H(h_xT, d_xT, row);
+    if (h_traj) GRID_D2H(h_traj, d_traj, e.traj);
+    if (h_xT) GRID_D2H(h_xT, d_xT, e.row);
     if (d_fx) GRID_D2H(h_fx, d_fx, fx_count);
     if (d_fu) GRID_D2H(h_fu, d_fu, fu_count);
     GRID_TRY(hipStreamSynchronize(s));
@@ -865,80 +852,61 @@ static int rollout_linearized_host(grid_handle *h, const T *h_x0, int stride_x0,
 // The reverse pass over a stored trajectory: grad_x0 and grad_u of a cost whose gradient with respect to the states is gx (every step) and / or gxT (the final state).
 template <typename T>
 static int rollout_adjoint_check(const T *traj, const T *u, long stride_u_step, int stride_u_solve, int N, int num_steps, const T *gx, const T *gxT, const T *grad_x0, const T *grad_u) {
-    if (num_steps < 0) return fail_msg(hipErrorInvalidValue, "negative num_steps");
-    if (N == 0) return 0;
-    if (num_steps > 0 && (!traj || !u)) return fail_msg(hipErrorInvalidValue, "null input pointer: traj and u must be given");
-    if (!gx && !gxT) return fail_msg(hipErrorInvalidValue, "null cotangents: at least one of gx and gxT must be given");
-    if (!grad_x0 && !grad_u) return fail_msg(hipErrorInvalidValue, "null output pointers: at least one of grad_x0 and grad_u must be given");
     const int n = (int)grid::NUM_JOINTS;
+    const int rc = check_rollout_call(N, num_steps, num_steps == 0 || (traj && u), "null input pointer: traj and u must be given", grad_x0 || grad_u,
+                                      "null output pointers: at least one of grad_x0 and grad_u must be given", 2 * n, stride_u_step, stride_u_solve);
+    if (rc || N == 0) return rc;
+    if (!gx && !gxT) return fail_msg(hipErrorInvalidValue, "null cotangents: at least one of gx and gxT must be given");
     if ((long)N * 2 * n > (long)INT_MAX) return fail_msg(hipErrorInvalidValue, "2n * num_solves exceeds the 32-bit offsets the kernel uses inside one step");
-    return check_rollout_strides(2 * n, stride_u_step, stride_u_solve, N, num_steps);
+    return 0;
 }
 
 template <typename T>
 static int rollout_adjoint_device(grid_handle *h, const T *d_traj, const T *d_u, long stride_u_step, int stride_u_solve, int N, int num_steps, T dt, T gravity,
                                   const T *d_gx, const T *d_gxT, T *d_grad_x0, T *d_grad_u, void *stream) {
     int rc = check_args(h, N);
-    if (rc) return rc;
-    if ((rc = rollout_adjoint_check<T>(d_traj, d_u, stride_u_step, stride_u_solve, N, num_steps, d_gx, d_gxT, d_grad_x0, d_grad_u))) return rc;
-    if (N == 0) return 0;
-    if (num_steps == 0 && !d_grad_x0) return 0;  // (no step: no grad_u is written)
-    GRID_ON_DEVICE(h);
-    if ((rc = ensure_typed<T>(h))) return rc;
-    launch_cfg c;
-    if ((rc = make_launch<T>(h, N, grid::ROLLOUT_ADJ_SUGGESTED_THREADS, grid::GRID_MAX_SOLVES_PER_BLOCK, grid::ROLLOUT_ADJ_LDS_PER_SOLVE, grid::ROLLOUT_ADJ_OUT_PER_SOLVE, &c))) return rc;
-    hipLaunchKernelGGL((grid::rollout_adjoint_kernel<T>), c.grid, c.block, c.lds, (hipStream_t)stream, d_grad_x0, num_steps > 0 ? d_grad_u : static_cast<T *>(nullptr), d_traj, d_u,
-                       stride_u_step, stride_u_solve, d_gx, d_gxT, typed<T>(h).d_robotModel, dt, gravity, N, num_steps);
-    GRID_TRY(hipGetLastError());
-    return 0;
+    if (!rc) rc = rollout_adjoint_check<T>(d_traj, d_u, stride_u_step, stride_u_solve, N, num_steps, d_gx, d_gxT, d_grad_x0, d_grad_u);
+    if (!rc && num_steps == 0 && !d_grad_x0) return 0;  // (no step: no grad_u is written)
+    device_launch<T> L(h, N, shape::ROLLOUT_ADJ, rc);
+    if (!L.ready) return L.rc;
+    hipLaunchKernelGGL((grid::rollout_adjoint_kernel<T>), L.grid, L.block, L.lds, (hipStream_t)stream, d_grad_x0, num_steps > 0 ? d_grad_u : static_cast<T *>(nullptr), d_traj, d_u,
+                       stride_u_step, stride_u_solve, d_gx, d_gxT, L.model, dt, gravity, N, num_steps);
+    return launch_status();
 }
 
 // Host buffers in, host buffers out, synchronous.  traj and u pass through the handle's d_x_traj / d_u_traj like rollout_host, gx, gxT and the two gradients through
-// hd_data->d_gx_traj / d_gx0 / d_gu_traj (null after init_gridData, allocated here on first use, grown by longer calls, freed by close_grid; gxT rides behind gx).
-// No staged record may exceed GRID_ROLLOUT_LIN_HOST_CAP_BYTES: such a call is refused before anything is allocated or copied.
+// hd_data->d_gx_traj / d_gx0 / d_gu_traj (same rules; gxT rides behind gx).  Subject to check_rollout_staging.
 template <typename T>
 static int rollout_adjoint_host(grid_handle *h, const T *h_traj, const T *h_u, long stride_u_step, int stride_u_solve, int N, int num_steps, T dt, T gravity,
                                 const T *h_gx, const T *h_gxT, T *h_grad_x0, T *h_grad_u) {
     int rc = host_prologue<T>(h, N);
-    if (rc) return rc;
-    if ((rc = rollout_adjoint_check<T>(h_traj, h_u, stride_u_step, stride_u_solve, N, num_steps, h_gx, h_gxT, h_grad_x0, h_grad_u))) return rc;
-    if (N == 0) return 0;
-    const size_t n = grid::NUM_JOINTS;
-    const size_t u_span = stride_u_solve == 0 ? n : (size_t)(N - 1) * stride_u_solve + n;
-    const size_t u_count = num_steps > 0 ? (size_t)(num_steps - 1) * (size_t)stride_u_step + u_span : 0;
-    const size_t row = 2 * n * (size_t)N;
-    const size_t x_count = row * ((size_t)num_steps + 1);
-    const size_t gx_count = (h_gx ? x_count : 0) + (h_gxT ? row : 0);
-    const size_t gu_count = h_grad_u ? n * (size_t)N * (size_t)num_steps : 0;
-    const size_t cap = GRID_ROLLOUT_LIN_HOST_CAP_BYTES / sizeof(T);
-    if (x_count > cap || gx_count > cap || u_count > cap) {
-        snprintf(g_err, sizeof(g_err), "rollout_adjoint host staging capacity exceeded: %d solves x %d steps need %zu bytes for the largest record, the cap is %zu "
-                 "(split the horizon or use the device entry point)", N, num_steps,
-                 (gx_count > x_count ? (gx_count > u_count ? gx_count : u_count) : (x_count > u_count ? x_count : u_count)) * sizeof(T), (size_t)GRID_ROLLOUT_LIN_HOST_CAP_BYTES);
-        return (int)hipErrorInvalidValue;
-    }
+    if (!rc) rc = rollout_adjoint_check<T>(h_traj, h_u, stride_u_step, stride_u_solve, N, num_steps, h_gx, h_gxT, h_grad_x0, h_grad_u);
+    if (rc || N == 0) return rc;
+    const rollout_counts e = rollout_extent(stride_u_step, stride_u_solve, N, num_steps);
+    const size_t gx_count = (h_gx ? e.traj : 0) + (h_gxT ? e.row : 0);
+    const size_t gu_count = h_grad_u ? (size_t)grid::NUM_JOINTS * (size_t)N * (size_t)num_steps : 0;
+    if ((rc = check_rollout_staging("rollout_adjoint", N, num_steps, {e.traj, gx_count, e.u}, sizeof(T)))) return rc;
     if (num_steps == 0 && !h_grad_x0) return 0;
     GRID_ON_DEVICE(h);
     if ((rc = ensure_typed<T>(h))) return rc;
     grid::gridData<T> *d = typed<T>(h).hd_data;
     {
         std::lock_guard<std::mutex> lock(h->alloc_lock);
-        if ((rc = ee_grow<T>(&d->d_u_traj, &typed<T>(h).u_traj_cap, u_count > 0 ? u_count : 1))) return rc;
-        if ((rc = ee_grow<T>(&d->d_x_traj, &typed<T>(h).x_traj_cap, x_count))) return rc;
-        if ((rc = ee_grow<T>(&d->d_gx_traj, &typed<T>(h).gx_traj_cap, gx_count))) return rc;
-        if (gu_count > 0 && (rc = ee_grow<T>(&d->d_gu_traj, &typed<T>(h).gu_traj_cap, gu_count))) return rc;
-        if (h_grad_x0 && (rc = ee_grow<T>(&d->d_gx0, &typed<T>(h).gx0_cap, row))) return rc;
+        if ((rc = grow_staging<T>(&d->d_u_traj, &typed<T>(h).u_traj_cap, e.u > 0 ? e.u : 1))) return rc;
+        if ((rc = grow_staging<T>(&d->d_x_traj, &typed<T>(h).x_traj_cap, e.traj))) return rc;
+        if ((rc = grow_staging<T>(&d->d_gx_traj, &typed<T>(h).gx_traj_cap, gx_count))) return rc;
+        if (gu_count > 0 && (rc = grow_staging<T>(&d->d_gu_traj, &typed<T>(h).gu_traj_cap, gu_count))) return rc;
+        if (h_grad_x0 && (rc = grow_staging<T>(&d->d_gx0, &typed<T>(h).gx0_cap, e.row))) return rc;
     }
-    const T *d_gx = h_gx ? d->d_gx_traj : nullptr;
-    const T *d_gxT = h_gxT ? d->d_gx_traj + (h_gx ? x_count : 0) : nullptr;
+    T *d_gx = h_gx ? d->d_gx_traj : nullptr, *d_gxT = h_gxT ? d->d_gx_traj + (h_gx ? e.traj : 0) : nullptr;
     T *d_grad_x0 = h_grad_x0 ? d->d_gx0 : nullptr, *d_grad_u = gu_count > 0 ? d->d_gu_traj : nullptr;
     hipStream_t s = h->streams[0];
-    if (num_steps > 0) GRID_H2D(d->d_x_traj, h_traj, row * (size_t)num_steps);  // (row num_steps of traj is not read)
-    if (u_count > 0) GRID_H2D(d->d_u_traj, h_u, u_count);
-    if (h_gx) GRID_H2D(d->d_gx_traj, h_gx, x_count);
-    if (h_gxT) GRID_H2D(d->d_gx_traj + (h_gx ? x_count : 0), h_gxT, row);
+    if (num_steps > 0) GRID_H2D(d->d_x_traj, h_traj, e.row * (size_t)num_steps);  // (row num_steps of traj is not read)
+    if (e.u > 0) GRID_H2D(d->d_u_traj, h_u, e.u);
+    if (h_gx) GRID_H2D(d_gx, h_gx, e.traj);
+    if (h_gxT) GRID_H2D(d_gxT, h_gxT, e.row);
     if ((rc = rollout_adjoint_device<T>(h, d->d_x_traj, d->d_u_traj, stride_u_step, stride_u_solve, N, num_steps, dt, gravity, d_gx, d_gxT, d_grad_x0, d_grad_u, (void *)s))) return rc;
-    if (d_grad_x0) GRID_D2H(h_grad_x0, d_grad_x0, row);
+    if (d_grad_x0) GRID_D2H(h_grad_x0, d_grad_x0, e.row);
     if (d_grad_u) GRID_D2H(h_grad_u, d_grad_u, gu_count);
     GRID_TRY(hipStreamSynchronize(s));
     return 0;
@@ -990,7 +958,7 @@ int grid_suggested_threads(void) { return grid::SUGGESTED_THREADS; }
 int grid_lds_bytes_per_block(void) {  // what a default forward_dynamics_gradient launch asks for (same arithmetic as make_launch)
     grid_handle h{};
     launch_cfg c;
-    if (make_launch<float>(&h, 1, grid::FD_DU_SUGGESTED_THREADS, grid::GRID_MAX_SOLVES_PER_BLOCK, grid::FD_DU_LDS_PER_SOLVE, grid::FD_DU_OUT_PER_SOLVE, &c)) return -1;
+    if (make_launch<float>(&h, 1, shape::FD_DU, &c)) return -1;
     return (int)c.lds;
 }
 int grid_has_second_order(void) { return GRID_HAS_IDSVA_SO; }

@@ -261,25 +261,47 @@ class GridLibrary:
     def crba_host(self, q):
         return self._crba_host(q, np.float32)
 
-    # ---- fused rollout: x0 (N, 2n | 3n) rows starting with [q | qd], u (T, N, n) or one shared sequence (T, n) -> traj (T+1, N, 2n) or xT (N, 2n)
-    def _rollout_host(self, x0, u, dt, final_only, gravity, dtype):
+    # ---- the rollout family: what its entry points share
+    def _typed(self, name, f64):
+        """(ctypes type of a real argument, entry point `name` of the library) in double or single precision"""
+        return (ctypes.c_double, getattr(self.lib, name + "_f64")) if f64 else (ctypes.c_float, getattr(self.lib, name))
+
+    def _u_strides(self, N, shared):
+        """(stride_u_step, stride_u_solve) of a dense control (T, N, n), or of ONE sequence (T, n) shared by all solves"""
+        return (self.n, 0) if shared else (N * self.n, self.n)
+
+    def _u_layout(self, u, N, dtype=None, T=None):
+        """(uu, T, stride_u_step, stride_u_solve) of a control of shape (T, N, n), or (T, n) shared by all solves.  dtype: u becomes a C-contiguous NumPy array
+        of it (None: u, e.g. a torch tensor, is taken as it is); T: the number of steps u must have (the adjoint knows it from traj)."""
+        n = self.n
+        uu = u if dtype is None else np.ascontiguousarray(u, dtype=dtype)
+        shared = uu.ndim == 2
+        if tuple(uu.shape[1:]) != ((n,) if shared else (N, n)) or (T is not None and uu.shape[0] != T):
+            raise ValueError("u must have shape (T, N, n) or (T, n) with %sN = %d, n = %d" % ("" if T is None else "T = %d, " % T, N, n))
+        return (uu, uu.shape[0]) + self._u_strides(N, shared)
+
+    def _rollout_forward_host(self, name, x0, u, dt, gravity, dtype, want, outputs):
+        """The host entry point `name` of rollout / rollout_linearized; outputs: what it can write, in the order of its arguments; want: what it is asked for."""
         n = self.n
         x = self._host_in(x0, (2 * n, 3 * n), "x0", dtype)
         N = x.shape[0]
-        uu = np.ascontiguousarray(u, dtype=dtype)
-        if uu.ndim == 2 and uu.shape[1] == n:
-            T, stride_solve, stride_step = uu.shape[0], 0, n
-        elif uu.ndim == 3 and uu.shape[1:] == (N, n):
-            T, stride_solve, stride_step = uu.shape[0], n, N * n
-        else:
-            raise ValueError("u must have shape (T, N, n) or (T, n) with N = %d, n = %d" % (N, n))
-        out = np.empty((N, 2 * n) if final_only else (T + 1, N, 2 * n), dtype=dtype)
-        real = ctypes.c_double if dtype == np.float64 else ctypes.c_float
-        fn = self.lib.grid_rollout_host_f64 if dtype == np.float64 else self.lib.grid_rollout_host
-        null, res = ctypes.c_void_p(None), ctypes.c_void_p(out.ctypes.data)
+        uu, T, stride_step, stride_solve = self._u_layout(u, N, dtype)
+        shapes = {"traj": (T + 1, N, 2 * n), "xT": (N, 2 * n), "fx": (T, N, 2 * n * n), "fu": (T, N, n * n)}
+        out = {k: np.empty(shapes[k], dtype=dtype) for k in want}
+        real, fn = self._typed(name, dtype == np.float64)
         self._check(fn(self.handle, ctypes.c_void_p(x.ctypes.data), ctypes.c_int(x.shape[1]), ctypes.c_void_p(uu.ctypes.data if uu.size else None), ctypes.c_long(stride_step),
-                       ctypes.c_int(stride_solve), ctypes.c_int(N), ctypes.c_int(T), real(dt), real(gravity), null if final_only else res, res if final_only else null))
-        return out
+                       ctypes.c_int(stride_solve), ctypes.c_int(N), ctypes.c_int(T), real(dt), real(gravity), *[ctypes.c_void_p(out[k].ctypes.data if k in out else None) for k in outputs]))
+        return tuple(out[k] for k in want)
+
+    def _rollout_forward_device(self, fn, real, d_x0, stride_x0, d_u, N, T, dt, outputs, u_shared, gravity, stream):
+        """The device entry point fn of rollout / rollout_linearized; outputs: its output arguments"""
+        stride_step, stride_solve = self._u_strides(N, u_shared)
+        self._check(fn(self.handle, _ptr(d_x0), ctypes.c_int(stride_x0 or 2 * self.n), _ptr(d_u), ctypes.c_long(stride_step), ctypes.c_int(stride_solve), ctypes.c_int(N), ctypes.c_int(T),
+                       real(dt), real(gravity), *[_ptr(o) for o in outputs], ctypes.c_void_p(stream)))
+
+    # ---- fused rollout: x0 (N, 2n | 3n) rows starting with [q | qd], u (T, N, n) or one shared sequence (T, n) -> traj (T+1, N, 2n) or xT (N, 2n)
+    def _rollout_host(self, x0, u, dt, final_only, gravity, dtype):
+        return self._rollout_forward_host("grid_rollout_host", x0, u, dt, gravity, dtype, ("xT",) if final_only else ("traj",), ("traj", "xT"))[0]
 
     def rollout_host(self, x0, u, dt, final_only=False, gravity=9.81):
         """T steps of ABA + semi-implicit Euler in one launch: the float32 trajectory (T+1, N, 2n) with row 0 = x0, or with final_only the last state (N, 2n)"""
@@ -290,24 +312,7 @@ class GridLibrary:
 
     # ---- linearised rollout: the trajectory and, per step, fx = [d qdd/dq | d qdd/dqd] (df_du records) and fu = d qdd/du = M^-1 (dense, symmetric)
     def _rollout_linearized_host(self, x0, u, dt, gravity, dtype, want=("traj", "fx", "fu")):
-        n = self.n
-        x = self._host_in(x0, (2 * n, 3 * n), "x0", dtype)
-        N = x.shape[0]
-        uu = np.ascontiguousarray(u, dtype=dtype)
-        if uu.ndim == 2 and uu.shape[1] == n:
-            T, stride_solve, stride_step = uu.shape[0], 0, n
-        elif uu.ndim == 3 and uu.shape[1:] == (N, n):
-            T, stride_solve, stride_step = uu.shape[0], n, N * n
-        else:
-            raise ValueError("u must have shape (T, N, n) or (T, n) with N = %d, n = %d" % (N, n))
-        shapes = {"traj": (T + 1, N, 2 * n), "xT": (N, 2 * n), "fx": (T, N, 2 * n * n), "fu": (T, N, n * n)}
-        out = {k: np.empty(shapes[k], dtype=dtype) for k in want}
-        P = lambda k: ctypes.c_void_p(out[k].ctypes.data) if k in out else ctypes.c_void_p(None)
-        real = ctypes.c_double if dtype == np.float64 else ctypes.c_float
-        fn = self.lib.grid_rollout_linearized_host_f64 if dtype == np.float64 else self.lib.grid_rollout_linearized_host
-        self._check(fn(self.handle, ctypes.c_void_p(x.ctypes.data), ctypes.c_int(x.shape[1]), ctypes.c_void_p(uu.ctypes.data if uu.size else None), ctypes.c_long(stride_step),
-                       ctypes.c_int(stride_solve), ctypes.c_int(N), ctypes.c_int(T), real(dt), real(gravity), P("traj"), P("xT"), P("fx"), P("fu")))
-        return tuple(out[k] for k in want)
+        return self._rollout_forward_host("grid_rollout_linearized_host", x0, u, dt, gravity, dtype, want, ("traj", "xT", "fx", "fu"))
 
     def rollout_linearized_host(self, x0, u, dt, gravity=9.81, want=("traj", "fx", "fu")):
         """T steps of (forward dynamics gradient, M^-1, semi-implicit Euler) in one launch -> (traj (T+1, N, 2n), fx (T, N, 2n^2), fu (T, N, n^2)) in float32;
@@ -325,13 +330,7 @@ class GridLibrary:
         if tr.ndim != 3 or tr.shape[2] != 2 * n:
             raise ValueError("traj must have shape (T+1, N, 2n) with n = %d" % n)
         T, N = tr.shape[0] - 1, tr.shape[1]
-        uu = np.ascontiguousarray(u, dtype=dtype)
-        if uu.ndim == 2 and uu.shape == (T, n):
-            stride_solve, stride_step = 0, n
-        elif uu.ndim == 3 and uu.shape == (T, N, n):
-            stride_solve, stride_step = n, N * n
-        else:
-            raise ValueError("u must have shape (T, N, n) or (T, n) with T = %d, N = %d, n = %d" % (T, N, n))
+        uu, _, stride_step, stride_solve = self._u_layout(u, N, dtype, T)
         want = tuple(want)
         if not want or any(k not in ("grad_x0", "grad_u") for k in want):
             raise ValueError('want must name "grad_x0" and / or "grad_u"')
@@ -344,8 +343,7 @@ class GridLibrary:
         shapes = {"grad_x0": (N, 2 * n), "grad_u": (T, N, n)}
         out = {k: np.empty(shapes[k], dtype=dtype) for k in want}
         P = lambda a: ctypes.c_void_p(a.ctypes.data if a is not None and a.size else None)
-        real = ctypes.c_double if dtype == np.float64 else ctypes.c_float
-        fn = self.lib.grid_rollout_adjoint_host_f64 if dtype == np.float64 else self.lib.grid_rollout_adjoint_host
+        real, fn = self._typed("grid_rollout_adjoint_host", dtype == np.float64)
         self._check(fn(self.handle, P(tr), P(uu), ctypes.c_long(stride_step), ctypes.c_int(stride_solve), ctypes.c_int(N), ctypes.c_int(T), real(dt), real(gravity),
                        P(g), P(gT), P(out.get("grad_x0")), P(out.get("grad_u"))))
         return tuple(out[k] for k in want)
@@ -480,22 +478,16 @@ class GridLibrary:
     def rollout_device(self, d_x0, d_u, N, T, dt, d_traj=None, d_xT=None, stride_x0=None, u_shared=False, gravity=9.81, stream=0):
         """Asynchronous on `stream`, allocates nothing.  d_x0: rows of stride_x0 (default 2n) values starting with [q | qd]; d_u: dense (T, N, n), or with u_shared
         ONE sequence (T, n) for all solves; d_traj (T+1, N, 2n) and / or d_xT (N, 2n): at least one of them."""
-        n = self.n
-        self._check(self.lib.grid_rollout_device(self.handle, _ptr(d_x0), ctypes.c_int(stride_x0 or 2 * n), _ptr(d_u), ctypes.c_long(n if u_shared else N * n),
-                                                 ctypes.c_int(0 if u_shared else n), ctypes.c_int(N), ctypes.c_int(T), ctypes.c_float(dt), ctypes.c_float(gravity),
-                                                 _ptr(d_traj), _ptr(d_xT), ctypes.c_void_p(stream)))
+        self._rollout_forward_device(self.lib.grid_rollout_device, ctypes.c_float, d_x0, stride_x0, d_u, N, T, dt, (d_traj, d_xT), u_shared, gravity, stream)
 
     def rollout_linearized_device(self, d_x0, d_u, N, T, dt, d_traj=None, d_xT=None, d_fx=None, d_fu=None, stride_x0=None, u_shared=False, gravity=9.81, stream=0):
         """Asynchronous on `stream`, allocates nothing.  Inputs as rollout_device; outputs (torch tensors or raw addresses, float32, each optional, at least one):
         d_traj (T+1, N, 2n), d_xT (N, 2n), d_fx (T, N, 2n^2), d_fu (T, N, n^2)."""
-        n = self.n
-        self._check(self.lib.grid_rollout_linearized_device(self.handle, _ptr(d_x0), ctypes.c_int(stride_x0 or 2 * n), _ptr(d_u), ctypes.c_long(n if u_shared else N * n),
-                                                            ctypes.c_int(0 if u_shared else n), ctypes.c_int(N), ctypes.c_int(T), ctypes.c_float(dt), ctypes.c_float(gravity),
-                                                            _ptr(d_traj), _ptr(d_xT), _ptr(d_fx), _ptr(d_fu), ctypes.c_void_p(stream)))
+        self._rollout_forward_device(self.lib.grid_rollout_linearized_device, ctypes.c_float, d_x0, stride_x0, d_u, N, T, dt, (d_traj, d_xT, d_fx, d_fu), u_shared, gravity, stream)
 
     def _rollout_adjoint_device(self, fn, real, d_traj, d_u, N, T, dt, d_gx, d_gxT, d_grad_x0, d_grad_u, u_shared, gravity, stream):
-        n = self.n
-        self._check(fn(self.handle, _ptr(d_traj), _ptr(d_u), ctypes.c_long(n if u_shared else N * n), ctypes.c_int(0 if u_shared else n), ctypes.c_int(N), ctypes.c_int(T),
+        stride_step, stride_solve = self._u_strides(N, u_shared)
+        self._check(fn(self.handle, _ptr(d_traj), _ptr(d_u), ctypes.c_long(stride_step), ctypes.c_int(stride_solve), ctypes.c_int(N), ctypes.c_int(T),
                        real(dt), real(gravity), _ptr(d_gx), _ptr(d_gxT), _ptr(d_grad_x0), _ptr(d_grad_u), ctypes.c_void_p(stream)))
 
     def rollout_adjoint_device(self, d_traj, d_u, N, T, dt, d_gx=None, d_gxT=None, d_grad_x0=None, d_grad_u=None, u_shared=False, gravity=9.81, stream=0):
@@ -605,9 +597,6 @@ def _rollout_function():
         return _ROLLOUT_FUNCTION
     import torch
 
-    def _real(t):
-        return ctypes.c_double if t.dtype == torch.float64 else ctypes.c_float
-
     def _stream(t):
         return torch.cuda.current_stream(t.device).cuda_stream
 
@@ -624,9 +613,9 @@ def _rollout_function():
             if gx0 is None and gu is None:
                 return None, (torch.zeros_like(u) if want_u else None)
             if traj.is_cuda:
-                fn = lib.lib.grid_rollout_adjoint_device_f64 if traj.dtype == torch.float64 else lib.lib.grid_rollout_adjoint_device
+                real, fn = lib._typed("grid_rollout_adjoint_device", traj.dtype == torch.float64)
                 with torch.cuda.device(traj.device):
-                    lib._rollout_adjoint_device(fn, _real(traj), traj, u, N, T, dt, g, None, gx0, gu, shared, gravity, _stream(traj))
+                    lib._rollout_adjoint_device(fn, real, traj, u, N, T, dt, g, None, gx0, gu, shared, gravity, _stream(traj))
             else:
                 f = lib.rollout_adjoint_host_f64 if traj.dtype == torch.float64 else lib.rollout_adjoint_host
                 res = f(traj.numpy(), u.numpy(), dt, gx=g.numpy(), gravity=gravity, want=tuple(k for k, w in (("grad_x0", gx0 is not None), ("grad_u", gu is not None)) if w))
@@ -651,17 +640,13 @@ def _rollout_function():
             if x0.dim() != 2 or x0.shape[1] != 2 * n:
                 raise ValueError("x0 must have shape (N, 2n) with n = %d" % n)
             N = x0.shape[0]
-            if not ((u.dim() == 2 and u.shape[1] == n) or (u.dim() == 3 and tuple(u.shape[1:]) == (N, n))):
-                raise ValueError("u must have shape (T, N, n) or (T, n) with N = %d, n = %d" % (N, n))
-            x0c, uc = x0.detach().contiguous(), u.detach().contiguous()
-            T, shared = uc.shape[0], uc.dim() == 2
+            x0c = x0.detach().contiguous()
+            uc, T, _, _ = lib._u_layout(u.detach().contiguous(), N)
             traj = torch.empty((T + 1, N, 2 * n), dtype=x0.dtype, device=x0.device)
             if x0.is_cuda:
-                fn = lib.lib.grid_rollout_device_f64 if x0.dtype == torch.float64 else lib.lib.grid_rollout_device
-                real = _real(x0)
+                real, fn = lib._typed("grid_rollout_device", x0.dtype == torch.float64)
                 with torch.cuda.device(x0.device):
-                    lib._check(fn(lib.handle, _ptr(x0c), ctypes.c_int(2 * n), _ptr(uc), ctypes.c_long(n if shared else N * n), ctypes.c_int(0 if shared else n), ctypes.c_int(N),
-                                  ctypes.c_int(T), real(dt), real(gravity), _ptr(traj), _ptr(None), ctypes.c_void_p(_stream(x0))))
+                    lib._rollout_forward_device(fn, real, x0c, 2 * n, uc, N, T, dt, (traj, None), uc.dim() == 2, gravity, _stream(x0))
             else:
                 f = lib.rollout_host_f64 if x0.dtype == torch.float64 else lib.rollout_host
                 traj.copy_(torch.from_numpy(f(x0c.numpy(), uc.numpy(), dt, gravity=gravity)))
