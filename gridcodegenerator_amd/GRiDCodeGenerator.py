@@ -172,6 +172,10 @@ class GRiDCodeGenerator:
     from .algorithms import gen_rollout_adjoint_layout, gen_rollout_adjoint_constants, gen_rollout_adjoint_prefetch, gen_rollout_linearize_device, gen_rollout_adjoint_device, gen_rollout_adjoint_kernel, \
         gen_rollout_adjoint_reserve, gen_rollout_adjoint_host, gen_rollout_adjoint
     from ._test import test_rollout_adjoint
+    # closed-loop rollout: linear feedback law and torque limits inside the fused step loop (no counterpart in the reference)
+    from .algorithms import gen_rollout_feedback_layout, gen_rollout_feedback_constants, gen_rollout_feedback_control_device, gen_rollout_feedback_kernel, \
+        gen_rollout_feedback_reserve, gen_rollout_feedback_host, gen_rollout_feedback
+    from ._test import test_rollout_feedback
 
     def __init__(self, robotObj, DEBUG_MODE=False, NEED_PRINT_MAT=False, USE_DYNAMIC_SHARED_MEM=True, FILE_NAMESPACE="grid", COLS_PER_LANE=None, tuning=None):
         if not USE_DYNAMIC_SHARED_MEM:
@@ -409,6 +413,8 @@ class GRiDCodeGenerator:
                                  "    T *d_fx_traj;", "    T *d_fu_traj;", "    T *h_fx_traj;", "    T *h_fu_traj;",
                                  "    // ROLLOUT ADJOINT (reserved by rollout_adjoint_reserve, not by init_gridData)",
                                  "    T *d_gx_traj;", "    T *d_gu_traj;", "    T *d_gx0;", "    T *h_gx_traj;", "    T *h_gu_traj;", "    T *h_gx0;",
+                                 "    // CLOSED-LOOP ROLLOUT (reserved by rollout_feedback_reserve, not by init_gridData)",
+                                 "    T *d_K_traj;", "    T *d_xref_traj;", "    T *d_uout_traj;", "    T *d_u_lim;", "    T *h_K_traj;", "    T *h_xref_traj;", "    T *h_uout_traj;", "    T *h_u_lim;",
                                  "};"])
 
     def gen_init_gridData(self):
@@ -418,7 +424,8 @@ class GRiDCodeGenerator:
                 ("h_Minv", "NUM_JOINTS*NUM_JOINTS"), ("h_qdd", "NUM_JOINTS"), ("h_dc_du", "NUM_JOINTS*2*NUM_JOINTS"), ("h_df_du", "NUM_JOINTS*2*NUM_JOINTS")]
         unused = ["d_M", "d_eePos", "d_deePos", "d_d2eePos", "d_idsva_so", "d_df2", "h_M", "h_eePos", "h_deePos", "h_d2eePos", "h_idsva_so", "h_df2",
                   "d_u_traj", "d_x_traj", "h_u_traj", "h_x_traj", "d_fx_traj", "d_fu_traj", "h_fx_traj", "h_fu_traj",
-                  "d_gx_traj", "d_gu_traj", "d_gx0", "h_gx_traj", "h_gu_traj", "h_gx0"]
+                  "d_gx_traj", "d_gu_traj", "d_gx0", "h_gx_traj", "h_gu_traj", "h_gx0",
+                  "d_K_traj", "d_xref_traj", "d_uout_traj", "d_u_lim", "h_K_traj", "h_xref_traj", "h_uout_traj", "h_u_lim"]
         if self.gen_idsva_so_available():
             dev += [("d_idsva_so", "4*NUM_JOINTS*NUM_JOINTS*NUM_JOINTS"), ("d_df2", "4*NUM_JOINTS*NUM_JOINTS*NUM_JOINTS")]
             host += [("h_idsva_so", "4*NUM_JOINTS*NUM_JOINTS*NUM_JOINTS"), ("h_df2", "4*NUM_JOINTS*NUM_JOINTS*NUM_JOINTS")]
@@ -485,6 +492,7 @@ class GRiDCodeGenerator:
                                  "grid_ee_release(&hd_data->d_u_traj, &hd_data->h_u_traj); grid_ee_release(&hd_data->d_x_traj, &hd_data->h_x_traj); // (allocated by rollout_reserve)",
                                  "grid_ee_release(&hd_data->d_fx_traj, &hd_data->h_fx_traj); grid_ee_release(&hd_data->d_fu_traj, &hd_data->h_fu_traj); // (allocated by rollout_linearized_reserve)",
                                  "grid_ee_release(&hd_data->d_gx_traj, &hd_data->h_gx_traj); grid_ee_release(&hd_data->d_gu_traj, &hd_data->h_gu_traj); grid_ee_release(&hd_data->d_gx0, &hd_data->h_gx0); // (allocated by rollout_adjoint_reserve)",
+                                 "grid_ee_release(&hd_data->d_K_traj, &hd_data->h_K_traj); grid_ee_release(&hd_data->d_xref_traj, &hd_data->h_xref_traj); grid_ee_release(&hd_data->d_uout_traj, &hd_data->h_uout_traj); grid_ee_release(&hd_data->d_u_lim, &hd_data->h_u_lim); // (allocated by rollout_feedback_reserve)",
                                  "free(hd_data);",
                                  "for(int i=0; i<" + str(MAX_STREAMS) + "; i++){gpuErrchk(hipStreamDestroy(streams[i]));} free(streams);"])
         self.gen_add_end_function()
@@ -562,6 +570,7 @@ class GRiDCodeGenerator:
             self.gen_rollout(use_thread_group)  # (outer namespace only; rollout_reserve uses grid_ee_reserve too)
             self.gen_rollout_linearized(use_thread_group)  # (after rollout: it calls grid_symplectic_euler_step and rollout_reserve)
             self.gen_rollout_adjoint(use_thread_group)  # (after rollout_linearized: same slice, same inners, reverse time)
+            self.gen_rollout_feedback(use_thread_group)  # (after every earlier member: their blocks keep their position; it calls rollout_device and rollout_reserve)
         if not self.nested:
             self.gen_init_close_grid()
 
@@ -648,6 +657,13 @@ class GRiDCodeGenerator:
                       "    __global__ rollout_adjoint_kernel<T>(T *d_grad_x0, T *d_grad_u, const T *d_traj, const T *d_u, const long stride_u_step, const int stride_u_solve, const T *d_gx, const T *d_gxT, const robotModel<T> *d_robotModel, const T dt, const T gravity, const int NUM_TIMESTEPS, const int NUM_STEPS)",
                       "    __host__   rollout_adjoint_reserve<T>(gridData<T> *hd_data, const int num_timesteps, const int num_steps)",
                       "    __host__   rollout_adjoint<T>(gridData<T> *hd_data, const robotModel<T> *d_robotModel, const T dt, const T gravity, const int num_timesteps, const int num_steps, const dim3 block_dimms, const dim3 thread_dimms, hipStream_t *streams)",
+                      "",
+                      "    closed-loop rollout, no counterpart in the reference: rollout with u_t = clamp(u_ff_t + K_t (x_t - x_ref_t)) formed inside the step loop (K (T, N, 2n^2) records K[c*n + j], x_ref (T, N, 2n), u_out (T, N, n);",
+                      "    a step or solve stride of 0 shares K / x_ref; one accumulator from u_ff, c ascending; limits optional: u_min, u_max of n values each):",
+                      "    __device__ rollout_feedback_control_device<T>(T *s_tau, T *s_dx, const T *s_q, const T *s_qd, const T *d_K_row, const T xref_q, const T xref_qd, const T u_ff, const T *d_u_min, const T *d_u_max, const int lane)",
+                      "    __global__ rollout_feedback_kernel<T>(T *d_traj, T *d_xT, T *d_u_out, const T *d_x0, const int stride_x0, const T *d_u, const long stride_u_step, const int stride_u_solve, const T *d_K, const long stride_K_step, const int stride_K_solve, const T *d_xref, const long stride_xref_step, const int stride_xref_solve, const T *d_u_min, const T *d_u_max, const robotModel<T> *d_robotModel, const T dt, const T gravity, const int NUM_TIMESTEPS, const int NUM_STEPS)",
+                      "    __host__   rollout_feedback_reserve<T>(gridData<T> *hd_data, const int num_timesteps, const int num_steps)",
+                      "    __host__   rollout_feedback<T>(gridData<T> *hd_data, const robotModel<T> *d_robotModel, const T dt, const T gravity, const int num_timesteps, const int num_steps, const bool use_limits, const dim3 block_dimms, const dim3 thread_dimms, hipStream_t *streams)",
                       "",
                       "Every host function also exists as NAME_single_timing and NAME_compute_only (no streams argument).",
                       "",

@@ -346,3 +346,34 @@ def test_rollout_adjoint(self, traj, U, dt, gx=None, gxT=None, GRAVITY=-9.81):
         grad_u[t] = dt * (0.5 * (Minv + Minv.T) @ w)
         lq, lv = g[t, :n] + lq + dt * (F[:, :n].T @ w), g[t, n:] + w + dt * (F[:, n:].T @ w)
     return np.concatenate([lq, lv]), grad_u
+
+
+def test_rollout_feedback(self, q, qd, U_ff, K, X_ref, dt, u_min=None, u_max=None, GRAVITY=-9.81):
+    """(states (T+1, 2n), applied controls (T, n)): test_rollout's integrator under the closed-loop law of rollout_feedback_kernel, in fp64.  U_ff (T, n), K (T, 2n^2)
+    records K[c*n + j] (or one record (2n^2,) for all steps), X_ref (>= T, 2n) (or one set point (2n,)), u_min / u_max (n,) both or neither:
+        u_t = clamp(U_ff[t] + K_t (x_t - X_ref[t]));  qdd = Minv(q_t) (u_t - c(q_t, qd_t));  qd_{t+1} = qd_t + dt qdd;  q_{t+1} = q_t + dt qd_{t+1}
+    with one accumulator per joint that starts from U_ff and takes the columns of K in ascending order, and the clamp v < u_min ? u_min : (v > u_max ? u_max : v)."""
+    n = self.model.n
+    q, qd = np.array(q, float), np.array(qd, float)
+    U_ff = np.asarray(U_ff, float).reshape(-1, n)
+    T = len(U_ff)
+    K = np.broadcast_to(np.asarray(K, float).reshape(-1, 2 * n * n), (T, 2 * n * n)) if np.size(K) == 2 * n * n else np.asarray(K, float).reshape(T, 2 * n * n)
+    X_ref = np.broadcast_to(np.asarray(X_ref, float).reshape(2 * n), (T, 2 * n)) if np.size(X_ref) == 2 * n else np.asarray(X_ref, float).reshape(-1, 2 * n)
+    if (u_min is None) != (u_max is None):
+        raise ValueError("u_min and u_max come together")
+    traj, applied = np.zeros((T + 1, 2 * n)), np.zeros((T, n))
+    traj[0] = np.concatenate([q, qd])
+    for t in range(T):
+        dx = traj[t] - X_ref[t]
+        v = U_ff[t].copy()
+        for c in range(2 * n):
+            v = v + K[t, c * n:(c + 1) * n] * dx[c]
+        if u_min is not None:
+            lo, hi = np.asarray(u_min, float), np.asarray(u_max, float)
+            v = np.where(v < lo, lo, np.where(v > hi, hi, v))
+        applied[t] = v
+        qdd = test_minv(self, q, True) @ (v - test_rnea(self, q, qd, None, GRAVITY)[0])
+        qd = qd + dt * qdd
+        q = q + dt * qd
+        traj[t + 1] = np.concatenate([q, qd])
+    return traj, applied

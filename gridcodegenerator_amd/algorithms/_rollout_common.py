@@ -1,4 +1,4 @@
-"""The skeleton the rollout family shares (rollout, rollout_linearized, rollout_adjoint), emitter helpers for the HIP/CDNA4 backend.
+"""The skeleton the rollout family shares (rollout, rollout_linearized, rollout_adjoint, rollout_feedback), emitter helpers for the HIP/CDNA4 backend.
 
 Every member is one kernel that keeps a solve's state in its LDS slice for NUM_STEPS steps, a *_reserve function for its gridData buffers and three host wrappers
 (plain, _single_timing, _compute_only).  What differs between the members in substance - the step functions and the bodies of the step loops - stays in their own
@@ -105,27 +105,31 @@ def gen_rollout_family_host(self, desc, mode):
     """One host wrapper of a member: mode 0 = H2D, launch, D2H; 1 = _single_timing (solve 0 alone, time per step printed); 2 = _compute_only (the launch alone).
     desc: name, tag (prefix of the member's constants and of the printf), doc (summary, notes of mode 0, what hd_data holds, "takes" / "took"),
     x0 (True where the kernel takes stride_x0), args (the kernel's arguments, as the launch spells them) and
-    h2d / d2h rows [(gridData field, values per solve, factor over the steps)]."""
+    h2d / d2h rows [(gridData field, values per solve, factor over the steps)]; a row with a fourth entry is not per solve: the entry is its whole count.
+    Optional: extra_params [(C++ parameter, its doc line)] that follow num_steps, setup (lines behind the strides; %(N)s is the number of solves of this mode)."""
     single_call_timing = mode == 1
     compute_only = mode == 2
     summary, notes, hd_data, takes = desc["doc"]
     func_params = ["hd_data is the packaged input and output pointers: " + hd_data,
                    "d_robotModel is the pointer to the initialized model specific helpers on the GPU (XImats, topology_helpers, etc.)",
                    "dt is the time step", "gravity is the gravity constant,",
-                   "num_timesteps is the number of independent solves (trajectories)", "num_steps is the number of steps every solve " + takes,
-                   "streams are pointers to HIP streams for async memory transfers (if needed)"]
+                   "num_timesteps is the number of independent solves (trajectories)", "num_steps is the number of steps every solve " + takes]
+    func_params += [doc for _, doc in desc.get("extra_params", [])]
+    func_params += ["streams are pointers to HIP streams for async memory transfers (if needed)"]
     suffix = ("_single_timing" if single_call_timing else "") + ("_compute_only" if compute_only else "")
     self.gen_add_func_doc(summary, notes if mode == 0 else [], func_params, None)
     self.gen_add_code_line("template <typename T>")
     self.gen_add_code_line("__host__")
-    self.gen_add_code_line("void " + desc["name"] + suffix + "(gridData<T> *hd_data, const robotModel<T> *d_robotModel, const T dt, const T gravity, const int num_timesteps, const int num_steps,")
+    self.gen_add_code_line("void " + desc["name"] + suffix + "(gridData<T> *hd_data, const robotModel<T> *d_robotModel, const T dt, const T gravity, const int num_timesteps, const int num_steps,"
+                           + "".join(" %s," % p for p, _ in desc.get("extra_params", [])))
     self.gen_add_code_line("                      const dim3 block_dimms, const dim3 thread_dimms" + ("" if compute_only else ", hipStream_t *streams") + ") {", True)
     N = "1" if single_call_timing else "num_timesteps"
     copy = lambda row, dst, src, tail: "gpuErrchk(hipMemcpy%s(hd_data->%s_%s,hd_data->%s_%s,static_cast<size_t>(%s)*%s%s*sizeof(T),%s));" \
-        % (("Async" if dst == "d" else ""), dst, row[0], src, row[0], row[1], N, row[2], tail)
+        % (("Async" if dst == "d" else ""), dst, row[0], src, row[0], row[1], N if len(row) < 4 else row[3], row[2], tail)
     self.gen_add_code_lines(["%s_reserve<T>(hd_data, %s, num_steps);" % (desc["name"], N),
                              ("const int stride_x0 = 3*NUM_JOINTS; " if desc["x0"] else "")
-                             + "const int stride_u_solve = NUM_JOINTS; const long stride_u_step = static_cast<long>(NUM_JOINTS)*%s;" % N])
+                             + "const int stride_u_solve = NUM_JOINTS; const long stride_u_step = static_cast<long>(NUM_JOINTS)*%s;" % N]
+                            + [ln % {"N": N} for ln in desc.get("setup", [])])
     if not compute_only:
         self.gen_add_code_line("// start code with memory transfer")
         self.gen_add_code_lines([copy(row, "d", "h", "hipMemcpyHostToDevice,streams[0]") for row in desc["h2d"]])

@@ -40,6 +40,7 @@ struct grid_typed {
     size_t u_traj_cap = 0, x_traj_cap = 0;  // elements of hd_data->d_u_traj / d_x_traj, the staging of the rollout host entry point (same rules)
     size_t fx_traj_cap = 0, fu_traj_cap = 0;  // elements of hd_data->d_fx_traj / d_fu_traj, the Jacobian staging of the linearised rollout host entry point (same rules)
     size_t gx_traj_cap = 0, gu_traj_cap = 0, gx0_cap = 0;  // elements of hd_data->d_gx_traj / d_gu_traj / d_gx0, the staging of the rollout adjoint host entry point (same rules)
+    size_t K_traj_cap = 0, xref_traj_cap = 0, uout_traj_cap = 0, u_lim_cap = 0;  // elements of hd_data->d_K_traj / d_xref_traj / d_uout_traj / d_u_lim, the staging of the closed-loop rollout host entry point (same rules)
 };
 
 // staging of the kinematics host entry points (grid_end_effector_pose*_host): allocated by the first kinematics call on a handle, never by grid_init,
@@ -160,6 +161,7 @@ constexpr kernel_shape EE[3] = {outer(grid::EE_POS_SUGGESTED_THREADS, grid::EE_P
 constexpr kernel_shape ROLLOUT = outer(grid::ROLLOUT_SUGGESTED_THREADS, grid::ROLLOUT_LDS_PER_SOLVE, grid::ROLLOUT_OUT_PER_SOLVE);
 constexpr kernel_shape ROLLOUT_LIN = outer(grid::ROLLOUT_LIN_SUGGESTED_THREADS, grid::ROLLOUT_LIN_LDS_PER_SOLVE, grid::ROLLOUT_LIN_OUT_PER_SOLVE);
 constexpr kernel_shape ROLLOUT_ADJ = outer(grid::ROLLOUT_ADJ_SUGGESTED_THREADS, grid::ROLLOUT_ADJ_LDS_PER_SOLVE, grid::ROLLOUT_ADJ_OUT_PER_SOLVE);
+constexpr kernel_shape ROLLOUT_FB = outer(grid::ROLLOUT_FB_SUGGESTED_THREADS, grid::ROLLOUT_FB_LDS_PER_SOLVE, grid::ROLLOUT_FB_OUT_PER_SOLVE);
 #if GRID_HAS_IDSVA_SO
 // (the second-order kernels of 8-lane robots run 16-lane groups: namespace wide)
 constexpr kernel_shape IDSVA_SO{grid_so::IDSVA_SO_SUGGESTED_THREADS, grid_so::IDSVA_SO_MAX_SOLVES_PER_BLOCK, grid_so::IDSVA_SO_LDS_PER_SOLVE, grid_so::IDSVA_SO_STAGE_PER_SOLVE, grid_so::GRID_LANES_PER_SOLVE};
@@ -912,6 +914,123 @@ static int rollout_adjoint_host(grid_handle *h, const T *h_traj, const T *h_u, l
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- closed-loop rollout
+// The rollout above with u_t = clamp(u_ff_t + K_t (x_t - x_ref_t)) formed inside the step loop.  K and x_ref are strided records: element (t, k, i) at
+// p[t*stride_step + k*stride_solve + i], i < rec.  A solve stride of 0 shares one record between the solves, a step stride of 0 between the steps; otherwise the
+// records of a step must not overlap and the steps must not either (a smaller or negative stride would read before / past the caller's buffer).
+static long feedback_span(long stride_solve, int N, long rec) {  // what one step of a strided record touches
+    return stride_solve == 0 ? rec : (long)(N - 1) * stride_solve + rec;
+}
+static int check_feedback_strides(const char *what, long rec, long stride_step, long stride_solve, int N, int num_steps) {
+    if (stride_step < 0 || stride_solve < 0) {
+        snprintf(g_err, sizeof(g_err), "negative stride of %s: stride_%s_step %ld, stride_%s_solve %ld", what, what, stride_step, what, stride_solve);
+        return (int)hipErrorInvalidValue;
+    }
+    if (stride_solve != 0 && stride_solve < rec) {
+        snprintf(g_err, sizeof(g_err), "stride_%s_solve %ld must be 0 (one record for all solves) or at least the %ld values of a record", what, stride_solve, rec);
+        return (int)hipErrorInvalidValue;
+    }
+    if (stride_solve > (long)INT_MAX || feedback_span(stride_solve, N, rec) > (long)INT_MAX) {
+        snprintf(g_err, sizeof(g_err), "stride_%s_solve * num_solves exceeds the 32-bit offsets the kernel uses inside one step", what);
+        return (int)hipErrorInvalidValue;
+    }
+    if (num_steps > 1 && stride_step != 0 && stride_step < feedback_span(stride_solve, N, rec)) {
+        snprintf(g_err, sizeof(g_err), "stride_%s_step %ld must be 0 (one record for all steps) or at least the %ld values one step spans", what, stride_step,
+                 feedback_span(stride_solve, N, rec));
+        return (int)hipErrorInvalidValue;
+    }
+    return 0;
+}
+static size_t feedback_extent(long rec, long stride_step, long stride_solve, int N, int num_steps) {  // elements the kernel may read
+    return num_steps > 0 ? (size_t)(num_steps - 1) * (size_t)stride_step + (size_t)feedback_span(stride_solve, N, rec) : 0;
+}
+
+// what both forms check after check_args / host_prologue; N == 0 is legal whatever the pointers are
+template <typename T>
+static int rollout_feedback_check(const T *x0, int stride_x0, const T *u_ff, long stride_u_step, int stride_u_solve, int N, int num_steps, const T *K, long stride_K_step,
+                                  long stride_K_solve, const T *x_ref, long stride_xref_step, long stride_xref_solve, const T *u_min, const T *u_max, const T *traj,
+                                  const T *xT, const T *u_out) {
+    const long n = grid::NUM_JOINTS;
+    int rc = check_rollout_call(N, num_steps, x0 && (num_steps == 0 || u_ff), "null input pointer", traj || xT || u_out,
+                                "null output pointers: at least one of traj, xT and u_out must be given", stride_x0, stride_u_step, stride_u_solve);
+    if (rc || N == 0) return rc;
+    if (num_steps > 0 && (!K || !x_ref)) return fail_msg(hipErrorInvalidValue, "null input pointer: K and x_ref must be given");
+    if ((u_min == nullptr) != (u_max == nullptr)) return fail_msg(hipErrorInvalidValue, "torque limits: u_min and u_max must be given together, or both be NULL");
+    if ((rc = check_feedback_strides("K", 2 * n * n, stride_K_step, stride_K_solve, N, num_steps))) return rc;
+    return check_feedback_strides("xref", 2 * n, stride_xref_step, stride_xref_solve, N, num_steps);
+}
+
+template <typename T>
+static int rollout_feedback_device(grid_handle *h, const T *d_x0, int stride_x0, const T *d_u, long stride_u_step, int stride_u_solve, int N, int num_steps, T dt, T gravity,
+                                   const T *d_K, long stride_K_step, long stride_K_solve, const T *d_xref, long stride_xref_step, long stride_xref_solve, const T *d_u_min,
+                                   const T *d_u_max, T *d_traj, T *d_xT, T *d_u_out, void *stream) {
+    int rc = check_args(h, N);
+    if (!rc) rc = rollout_feedback_check<T>(d_x0, stride_x0, d_u, stride_u_step, stride_u_solve, N, num_steps, d_K, stride_K_step, stride_K_solve, d_xref, stride_xref_step,
+                                            stride_xref_solve, d_u_min, d_u_max, d_traj, d_xT, d_u_out);
+    if (!rc && num_steps == 0 && !d_traj && !d_xT) return 0;  // (no step: no control is written)
+    device_launch<T> L(h, N, shape::ROLLOUT_FB, rc);
+    if (!L.ready) return L.rc;
+    hipLaunchKernelGGL((grid::rollout_feedback_kernel<T>), L.grid, L.block, L.lds, (hipStream_t)stream, d_traj, d_xT, num_steps > 0 ? d_u_out : static_cast<T *>(nullptr), d_x0,
+                       stride_x0, d_u, stride_u_step, stride_u_solve, d_K, stride_K_step, (int)stride_K_solve, d_xref, stride_xref_step, (int)stride_xref_solve, d_u_min, d_u_max,
+                       L.model, dt, gravity, N, num_steps);
+    return launch_status();
+}
+
+// Host buffers in, host buffers out, synchronous.  x0, u_ff and traj / xT as in rollout_host; K, x_ref, the limits and u_out pass through hd_data->d_K_traj /
+// d_xref_traj / d_u_lim / d_uout_traj (same rules).  K and x_ref are staged as the caller laid them out: a shared or time-invariant record is copied once.
+// Subject to check_rollout_staging.
+template <typename T>
+static int rollout_feedback_host(grid_handle *h, const T *h_x0, int stride_x0, const T *h_u, long stride_u_step, int stride_u_solve, int N, int num_steps, T dt, T gravity,
+                                 const T *h_K, long stride_K_step, long stride_K_solve, const T *h_xref, long stride_xref_step, long stride_xref_solve, const T *h_u_min,
+                                 const T *h_u_max, T *h_traj, T *h_xT, T *h_u_out) {
+    int rc = host_prologue<T>(h, N);
+    if (!rc) rc = rollout_feedback_check<T>(h_x0, stride_x0, h_u, stride_u_step, stride_u_solve, N, num_steps, h_K, stride_K_step, stride_K_solve, h_xref, stride_xref_step,
+                                            stride_xref_solve, h_u_min, h_u_max, h_traj, h_xT, h_u_out);
+    if (rc || N == 0) return rc;
+    const size_t n = grid::NUM_JOINTS;
+    if (stride_x0 > 3 * (int)n) return fail_msg(hipErrorInvalidValue, "stride_x0 must be in [2n, 3n] for host buffers");
+    const rollout_counts e = rollout_extent(stride_u_step, stride_u_solve, N, num_steps);
+    const rollout_x_layout x(e, h_traj, h_xT);
+    const size_t K_count = feedback_extent(2 * (long)(n * n), stride_K_step, stride_K_solve, N, num_steps);
+    const size_t xref_count = feedback_extent(2 * (long)n, stride_xref_step, stride_xref_solve, N, num_steps);
+    const size_t uout_count = h_u_out ? n * (size_t)N * (size_t)num_steps : 0;
+    if ((rc = check_rollout_staging("rollout_feedback", N, num_steps, {K_count, xref_count, uout_count, x.count, e.u}, sizeof(T)))) return rc;
+    if (num_steps == 0 && !h_traj && !h_xT) return 0;  // (no step: no control is written)
+    GRID_ON_DEVICE(h);
+    if ((rc = ensure_typed<T>(h))) return rc;
+    grid_typed<T> &t = typed<T>(h);
+    grid::gridData<T> *d = t.hd_data;
+    const bool limits = h_u_min != nullptr;
+    {
+        std::lock_guard<std::mutex> lock(h->alloc_lock);
+        if ((rc = grow_staging<T>(&d->d_u_traj, &t.u_traj_cap, e.u > 0 ? e.u : 1))) return rc;
+        if ((rc = grow_staging<T>(&d->d_x_traj, &t.x_traj_cap, x.count))) return rc;
+        if (K_count > 0 && (rc = grow_staging<T>(&d->d_K_traj, &t.K_traj_cap, K_count))) return rc;
+        if (xref_count > 0 && (rc = grow_staging<T>(&d->d_xref_traj, &t.xref_traj_cap, xref_count))) return rc;
+        if (uout_count > 0 && (rc = grow_staging<T>(&d->d_uout_traj, &t.uout_traj_cap, uout_count))) return rc;
+        if (limits && (rc = grow_staging<T>(&d->d_u_lim, &t.u_lim_cap, 2 * n))) return rc;
+    }
+    T *d_traj = h_traj ? d->d_x_traj : nullptr, *d_xT = h_xT ? d->d_x_traj + x.xT_offset : nullptr, *d_u_out = uout_count > 0 ? d->d_uout_traj : nullptr;
+    hipStream_t s = h->streams[0];
+    GRID_H2D(d->d_q_qd_u, h_x0, (size_t)stride_x0 * N);
+    if (e.u > 0) GRID_H2D(d->d_u_traj, h_u, e.u);
+    if (K_count > 0) GRID_H2D(d->d_K_traj, h_K, K_count);
+    if (xref_count > 0) GRID_H2D(d->d_xref_traj, h_xref, xref_count);
+    if (limits) {
+        GRID_H2D(d->d_u_lim, h_u_min, n);
+        GRID_H2D(d->d_u_lim + n, h_u_max, n);
+    }
+    if ((rc = rollout_feedback_device<T>(h, d->d_q_qd_u, stride_x0, d->d_u_traj, stride_u_step, stride_u_solve, N, num_steps, dt, gravity, d->d_K_traj, stride_K_step,
+                                         stride_K_solve, d->d_xref_traj, stride_xref_step, stride_xref_solve, limits ? d->d_u_lim : nullptr, limits ? d->d_u_lim + n : nullptr,
+                                         d_traj, d_xT, d_u_out, (void *)s)))
+        return rc;
+    if (h_traj) GRID_D2H(h_traj, d_traj, e.traj);
+    if (h_xT) GRID_D2H(h_xT, d_xT, e.row);
+    if (d_u_out) GRID_D2H(h_u_out, d_u_out, uout_count);
+    GRID_TRY(hipStreamSynchronize(s));
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- multi-GPU driver
 // One process, G handles (one per GPU): the batch [0, N) is cut into G contiguous ranges of ceil(N/G) solves (SURVEY.md section 8(e),
 // 16 384 total -> 16 384/G per GPU, no collective).  Every device has its own robotModel copy and stream.
@@ -1244,6 +1363,20 @@ int grid_rollout_linearized_host_f64(grid_handle *h, const double *h_x0, int str
                                      int num_steps, double dt, double gravity, double *h_traj, double *h_xT, double *h_fx, double *h_fu) {
     GRID_GUARDED(return rollout_linearized_host<double>(h, h_x0, stride_x0, h_u, stride_u_step, stride_u_solve, num_solves, num_steps, dt, gravity, h_traj, h_xT, h_fx, h_fu);)
 }
+#define GRID_FB_ARGS(T, p)                                                                                                                                         \
+    grid_handle *h, const T *p##_x0, int stride_x0, const T *p##_u_ff, long stride_u_step, int stride_u_solve, int num_solves, int num_steps, T dt, T gravity,       \
+        const T *p##_K, long stride_K_step, long stride_K_solve, const T *p##_x_ref, long stride_xref_step, long stride_xref_solve, const T *p##_u_min,                \
+        const T *p##_u_max, T *p##_traj, T *p##_xT, T *p##_u_out
+#define GRID_FB_PASS(p)                                                                                                                                          \
+    h, p##_x0, stride_x0, p##_u_ff, stride_u_step, stride_u_solve, num_solves, num_steps, dt, gravity, p##_K, stride_K_step, stride_K_solve, p##_x_ref, stride_xref_step, \
+        stride_xref_solve, p##_u_min, p##_u_max, p##_traj, p##_xT, p##_u_out
+int grid_rollout_feedback_device(GRID_FB_ARGS(float, d), void *stream) { GRID_GUARDED(return rollout_feedback_device<float>(GRID_FB_PASS(d), stream);) }
+int grid_rollout_feedback_host(GRID_FB_ARGS(float, h)) { GRID_GUARDED(return rollout_feedback_host<float>(GRID_FB_PASS(h));) }
+int grid_rollout_feedback_device_f64(GRID_FB_ARGS(double, d), void *stream) { GRID_GUARDED(return rollout_feedback_device<double>(GRID_FB_PASS(d), stream);) }
+int grid_rollout_feedback_host_f64(GRID_FB_ARGS(double, h)) { GRID_GUARDED(return rollout_feedback_host<double>(GRID_FB_PASS(h));) }
+#undef GRID_FB_ARGS
+#undef GRID_FB_PASS
+
 int grid_rollout_adjoint_device(grid_handle *h, const float *d_traj, const float *d_u, long stride_u_step, int stride_u_solve, int num_solves, int num_steps, float dt, float gravity,
                                 const float *d_gx, const float *d_gxT, float *d_grad_x0, float *d_grad_u, void *stream) {
     GRID_GUARDED(return rollout_adjoint_device<float>(h, d_traj, d_u, stride_u_step, stride_u_solve, num_solves, num_steps, dt, gravity, d_gx, d_gxT, d_grad_x0, d_grad_u, stream);)

@@ -358,6 +358,52 @@ class GridLibrary:
     def rollout_adjoint_host_f64(self, traj, u, dt, gx=None, gxT=None, gravity=9.81, want=("grad_x0", "grad_u")):
         return self._rollout_adjoint_host(traj, u, dt, gx, gxT, gravity, np.float64, want)
 
+    # ---- closed-loop rollout: u_t = clamp(u_ff_t + K_t (x_t - x_ref_t)) formed inside the fused step loop
+    def _feedback_layout(self, a, what, rec, N, T, dtype):
+        """(array, stride_step, stride_solve) of K (rec = 2n^2) or x_ref (rec = 2n): (>= T, N, rec) dense, (>= T, rec) shared by all solves, (rec,) one record for everything"""
+        aa = np.ascontiguousarray(a, dtype=dtype)
+        if aa.ndim == 3 and aa.shape[0] >= T and tuple(aa.shape[1:]) == (N, rec):
+            return aa, N * rec, rec
+        if aa.ndim == 2 and aa.shape[0] >= T and aa.shape[1] == rec:
+            return aa, rec, 0
+        if aa.ndim == 1 and aa.shape[0] == rec:
+            return aa, 0, 0
+        raise ValueError("%s must have shape (T, N, %d), (T, %d) or (%d,) with T %s %d, N = %d" % (what, rec, rec, rec, "=" if what == "K" else ">=", T, N))
+
+    def _rollout_feedback_host(self, x0, u_ff, K, x_ref, dt, u_min, u_max, want, gravity, dtype):
+        n = self.n
+        x = self._host_in(x0, (2 * n, 3 * n), "x0", dtype)
+        N = x.shape[0]
+        uu, T, su_step, su_solve = self._u_layout(u_ff, N, dtype)
+        KK, sK_step, sK_solve = self._feedback_layout(K, "K", 2 * n * n, N, T, dtype)
+        if KK.ndim > 1 and KK.shape[0] != T:
+            raise ValueError("K must have as many steps as u_ff (%d)" % T)
+        xr, sx_step, sx_solve = self._feedback_layout(x_ref, "x_ref", 2 * n, N, T, dtype)
+        if (u_min is None) != (u_max is None):
+            raise ValueError("u_min and u_max come together")
+        lim = [None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=dtype), (n,))) for a in (u_min, u_max)]
+        want = tuple(want)
+        if not want or any(k not in ("traj", "xT", "u") for k in want):
+            raise ValueError('want must name "traj", "xT" and / or "u"')
+        shapes = {"traj": (T + 1, N, 2 * n), "xT": (N, 2 * n), "u": (T, N, n)}
+        out = {k: np.empty(shapes[k], dtype=dtype) for k in want}
+        P = lambda a: ctypes.c_void_p(a.ctypes.data if a is not None and a.size else None)
+        real, fn = self._typed("grid_rollout_feedback_host", dtype == np.float64)
+        self._check(fn(self.handle, P(x), ctypes.c_int(x.shape[1]), P(uu), ctypes.c_long(su_step), ctypes.c_int(su_solve), ctypes.c_int(N), ctypes.c_int(T), real(dt), real(gravity),
+                       P(KK), ctypes.c_long(sK_step), ctypes.c_long(sK_solve), P(xr), ctypes.c_long(sx_step), ctypes.c_long(sx_solve), P(lim[0]), P(lim[1]),
+                       P(out.get("traj")), P(out.get("xT")), P(out.get("u"))))
+        return tuple(out[k] for k in want)
+
+    def rollout_feedback_host(self, x0, u_ff, K, x_ref, dt, u_min=None, u_max=None, want=("traj", "u"), gravity=9.81):
+        """T closed-loop steps in one launch -> (traj (T+1, N, 2n), u_applied (T, N, n)) in float32.  Per step u = clamp(u_ff + K (x - x_ref)), then ABA + semi-implicit
+        Euler as rollout_host.  x0, u_ff as x0, u of rollout_host; K (T, N, 2n^2) records K[c*n + j] (gain_records makes them), (T, 2n^2) shared by all solves, or (2n^2,) one
+        gain for everything; x_ref (>= T, N, 2n) (a nominal traj passes as it is), (>= T, 2n) shared by all solves, or (2n,) a set point; u_min, u_max: (n,) or scalars,
+        both or neither.  want: which of "traj", "xT", "u" to compute and return, in that order."""
+        return self._rollout_feedback_host(x0, u_ff, K, x_ref, dt, u_min, u_max, want, gravity, np.float32)
+
+    def rollout_feedback_host_f64(self, x0, u_ff, K, x_ref, dt, u_min=None, u_max=None, want=("traj", "u"), gravity=9.81):
+        return self._rollout_feedback_host(x0, u_ff, K, x_ref, dt, u_min, u_max, want, gravity, np.float64)
+
     def forward_dynamics_host(self, q_qd_u, gravity=9.81, aba=False):
         x = self._host_in(q_qd_u, 3 * self.n, "q_qd_u")
         out = np.empty((x.shape[0], self.n), dtype=np.float32)
@@ -499,6 +545,27 @@ class GridLibrary:
     def rollout_adjoint_device_f64(self, d_traj, d_u, N, T, dt, d_gx=None, d_gxT=None, d_grad_x0=None, d_grad_u=None, u_shared=False, gravity=9.81, stream=0):
         self._rollout_adjoint_device(self.lib.grid_rollout_adjoint_device_f64, ctypes.c_double, d_traj, d_u, N, T, dt, d_gx, d_gxT, d_grad_x0, d_grad_u, u_shared, gravity, stream)
 
+    def _rollout_feedback_device(self, f64, d_x0, d_uff, d_K, d_xref, N, T, dt, d_traj, d_xT, d_u_out, d_u_min, d_u_max, stride_x0, u_shared, K_strides, xref_strides, gravity, stream):
+        n = self.n
+        real, fn = self._typed("grid_rollout_feedback_device", f64)
+        su_step, su_solve = self._u_strides(N, u_shared)
+        sK_step, sK_solve = K_strides if K_strides is not None else (N * 2 * n * n, 2 * n * n)
+        sx_step, sx_solve = xref_strides if xref_strides is not None else (N * 2 * n, 2 * n)
+        self._check(fn(self.handle, _ptr(d_x0), ctypes.c_int(stride_x0 or 2 * n), _ptr(d_uff), ctypes.c_long(su_step), ctypes.c_int(su_solve), ctypes.c_int(N), ctypes.c_int(T),
+                       real(dt), real(gravity), _ptr(d_K), ctypes.c_long(sK_step), ctypes.c_long(sK_solve), _ptr(d_xref), ctypes.c_long(sx_step), ctypes.c_long(sx_solve),
+                       _ptr(d_u_min), _ptr(d_u_max), _ptr(d_traj), _ptr(d_xT), _ptr(d_u_out), ctypes.c_void_p(stream)))
+
+    def rollout_feedback_device(self, d_x0, d_uff, d_K, d_xref, N, T, dt, d_traj=None, d_xT=None, d_u_out=None, d_u_min=None, d_u_max=None,
+                                stride_x0=None, u_shared=False, K_strides=None, xref_strides=None, gravity=9.81, stream=0):
+        """Asynchronous on `stream`, allocates nothing.  d_x0, d_uff as d_x0, d_u of rollout_device; d_K dense (T, N, 2n^2) records K[c*n + j], d_xref dense (>= T, N, 2n), or
+        with K_strides / xref_strides = (step stride, solve stride) in elements, 0 sharing one record between the steps / the solves; d_u_min, d_u_max (n,), both or neither;
+        outputs d_traj (T+1, N, 2n), d_xT (N, 2n), d_u_out (T, N, n): at least one (torch tensors or raw addresses, float32)."""
+        self._rollout_feedback_device(False, d_x0, d_uff, d_K, d_xref, N, T, dt, d_traj, d_xT, d_u_out, d_u_min, d_u_max, stride_x0, u_shared, K_strides, xref_strides, gravity, stream)
+
+    def rollout_feedback_device_f64(self, d_x0, d_uff, d_K, d_xref, N, T, dt, d_traj=None, d_xT=None, d_u_out=None, d_u_min=None, d_u_max=None,
+                                    stride_x0=None, u_shared=False, K_strides=None, xref_strides=None, gravity=9.81, stream=0):
+        self._rollout_feedback_device(True, d_x0, d_uff, d_K, d_xref, N, T, dt, d_traj, d_xT, d_u_out, d_u_min, d_u_max, stride_x0, u_shared, K_strides, xref_strides, gravity, stream)
+
     def rollout_torch(self, x0, u, dt, gravity=9.81):
         """Differentiable rollout on torch tensors: traj (T+1, N, 2n) = rollout(x0, u) with autograd support.  x0 (N, 2n); u (T, N, n), or (T, n) shared by all
         solves (its gradient is the sum of the per-solve gradients over N); float32 or float64, x0 and u on the same device.  CUDA tensors go through the device
@@ -585,6 +652,18 @@ def discrete_jacobians(fx, fu, dt):
     A = cat([cat([top_q, top_v], -1), cat([low_q, low_v], -1)], -2)
     B = cat([(dt * dt) * M, dt * M], -2)
     return A, B
+
+
+def gain_records(K):
+    """Feedback gains as the closed-loop rollout reads them: row-major matrices K (..., n, 2n) (u = u_ff + K dx) -> records (..., 2n*n) with rec[c*n + j] = K[j, c],
+    the [col*n + row] storage of every matrix of the library.  NumPy in -> NumPy out; torch in -> torch out on the same device."""
+    if K.ndim < 2 or K.shape[-1] != 2 * K.shape[-2]:
+        raise ValueError("K must have shape (..., n, 2n)")
+    lead = tuple(K.shape[:-2])
+    size = K.shape[-1] * K.shape[-2]
+    if isinstance(K, np.ndarray):
+        return np.ascontiguousarray(np.swapaxes(K, -1, -2)).reshape(lead + (size,))
+    return K.transpose(-1, -2).contiguous().reshape(lead + (size,))
 
 
 _ROLLOUT_FUNCTION = None

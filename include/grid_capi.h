@@ -256,6 +256,46 @@ int grid_rollout_adjoint_device_f64(grid_handle *h, const double *d_traj, const 
 int grid_rollout_adjoint_host_f64(grid_handle *h, const double *h_traj, const double *h_u, long stride_u_step, int stride_u_solve, int num_solves, int num_steps, double dt,
                                   double gravity, const double *h_gx, const double *h_gxT, double *h_grad_x0, double *h_grad_u);
 
+/* Closed-loop rollout: the fused rollout with the control of every step formed INSIDE the step loop from the state the rollout has just reached - a time-varying
+ * linear feedback law and, optionally, torque limits.  Per solve k and step t (dynamics, gravity convention, damping and integrator of grid_rollout_*):
+ *   dx  = x_t - x_ref[t, k]                               x = [q ; qd], 2n values
+ *   v   = u_ff[t, k][j] + sum_c K[t, k][c*n + j]*dx[c]    one accumulator per joint j that starts from u_ff, c ascending 0 .. 2n-1
+ *   u_t = v, or with limits  v < u_min[j] ? u_min[j] : (v > u_max[j] ? u_max[j] : v)      (a NaN v stays NaN)
+ *   qdd = ABA(q_t, qd_t, u_t), then the semi-implicit Euler update of grid_rollout_*
+ * (iLQR / DDP forward pass: u_ff = u_bar + alpha*k, x_ref = the nominal trajectory.)  Layouts, time-major:
+ *   x0, traj, xT   exactly as grid_rollout_*
+ *   u_ff    as the u of grid_rollout_*: element (t, k, j) at u_ff[t*stride_u_step + k*stride_u_solve + j], same stride rules (stride_u_solve == 0: shared)
+ *   K       element (t, k, c*n + j) at K[t*stride_K_step + k*stride_K_solve + c*n + j]: the n x 2n gain stored [col*n + row] like every matrix of the library.
+ *           stride_K_step == 0: one gain for all steps; stride_K_solve == 0: one gain for all solves; otherwise stride_K_solve >= 2n^2 and stride_K_step
+ *           covers what one step spans.  Dense (num_steps, num_solves, 2n^2): stride_K_solve = 2n^2, stride_K_step = num_solves*2n^2
+ *   x_ref   element (t, k, i), i < 2n, at x_ref[t*stride_xref_step + k*stride_xref_solve + i].  stride_xref_step == 0: set-point regulation; stride_xref_solve == 0:
+ *           one reference for all solves; otherwise stride_xref_solve >= 2n and stride_xref_step covers what one step spans.  A nominal traj (num_steps+1,
+ *           num_solves, 2n) of grid_rollout_* passes as it is (row num_steps is not read)
+ *   u_min, u_max   n values each, shared by all solves and steps; both given or both NULL (no limits)
+ *   u_out   (num_steps, num_solves, n): the control that was applied, after the limits; may be NULL
+ * Every output may be NULL, but not all three.  num_steps == 0 copies x0 to traj / xT, writes no u_out and reads neither K nor x_ref.
+ * Errors (return code != 0, text in grid_last_error, handle stays usable): everything grid_rollout_* refuses, NULL K or x_ref with num_steps > 0, exactly one of
+ * u_min / u_max, all three outputs NULL, a K or x_ref solve stride that is neither 0 nor at least one record, a step stride that is neither 0 nor at least what one
+ * step spans, negative strides. */
+/* no counterpart in the reference (launches rollout_feedback_kernel<T>): device buffers, asynchronous on `stream`, nothing allocated */
+int grid_rollout_feedback_device(grid_handle *h, const float *d_x0, int stride_x0, const float *d_u_ff, long stride_u_step, int stride_u_solve, int num_solves, int num_steps,
+                                 float dt, float gravity, const float *d_K, long stride_K_step, long stride_K_solve, const float *d_x_ref, long stride_xref_step,
+                                 long stride_xref_solve, const float *d_u_min, const float *d_u_max, float *d_traj, float *d_xT, float *d_u_out, void *stream);
+/* no counterpart in the reference: host buffers, synchronous, stride_x0 in [2n, 3n], num_solves <= max_timesteps.  Everything is staged in device buffers of the
+ * handle that the first call allocates and longer calls grow (a shared or time-invariant K / x_ref is staged once); grid_close frees them.  Each staged record is
+ * capped at GRID_ROLLOUT_LIN_HOST_CAP_BYTES (1 GiB): a longer call returns hipErrorInvalidValue with a grid_last_error text before anything is allocated. */
+int grid_rollout_feedback_host(grid_handle *h, const float *h_x0, int stride_x0, const float *h_u_ff, long stride_u_step, int stride_u_solve, int num_solves, int num_steps,
+                               float dt, float gravity, const float *h_K, long stride_K_step, long stride_K_solve, const float *h_x_ref, long stride_xref_step,
+                               long stride_xref_solve, const float *h_u_min, const float *h_u_max, float *h_traj, float *h_xT, float *h_u_out);
+int grid_rollout_feedback_device_f64(grid_handle *h, const double *d_x0, int stride_x0, const double *d_u_ff, long stride_u_step, int stride_u_solve, int num_solves,
+                                     int num_steps, double dt, double gravity, const double *d_K, long stride_K_step, long stride_K_solve, const double *d_x_ref,
+                                     long stride_xref_step, long stride_xref_solve, const double *d_u_min, const double *d_u_max, double *d_traj, double *d_xT,
+                                     double *d_u_out, void *stream);
+int grid_rollout_feedback_host_f64(grid_handle *h, const double *h_x0, int stride_x0, const double *h_u_ff, long stride_u_step, int stride_u_solve, int num_solves,
+                                   int num_steps, double dt, double gravity, const double *h_K, long stride_K_step, long stride_K_solve, const double *h_x_ref,
+                                   long stride_xref_step, long stride_xref_solve, const double *h_u_min, const double *h_u_max, double *h_traj, double *h_xT,
+                                   double *h_u_out);
+
 /* in-kernel timing probe: replaces forward_dynamics_gradient_single_timing<T> (reference :236-248); returns microseconds per solve */
 int grid_forward_dynamics_gradient_single_timing(grid_handle *h, const float *h_q_qd_u, int reps, float gravity, float *h_df_du, double *us_per_call);
 

@@ -20,6 +20,7 @@ d_u, d_xT = torch.from_numpy(rng.uniform(-5, 5, (16, N, n)).astype(np.float32)).
 d_fx16, d_fu16 = torch.empty((16, N, 2 * n * n), dtype=torch.float32, device="cuda"), torch.empty((16, N, n * n), dtype=torch.float32, device="cuda")
 d_tr16, d_g16 = torch.from_numpy(rng.uniform(-1, 1, (17, N, 2 * n)).astype(np.float32)).cuda(), torch.from_numpy(rng.uniform(-1, 1, (17, N, 2 * n)).astype(np.float32)).cuda()
 d_gx0, d_gu16 = E(2 * n), torch.empty((16, N, n), dtype=torch.float32, device="cuda")
+d_K16 = torch.from_numpy(rng.uniform(-0.02, 0.02, (16, N, 2 * n * n)).astype(np.float32)).cuda()
 cases = [("inverse_dynamics", lambda: lib.inverse_dynamics_device(d_x, d_qdd, N, d_c, stream=st)),
          ("inverse_dynamics_gradient", lambda: lib.inverse_dynamics_gradient_device(d_x, d_qdd, N, d_g, stream=st)),
          ("direct_minv", lambda: lib.direct_minv_device(d_x, N, d_M, stream=st)),
@@ -29,6 +30,7 @@ cases = [("inverse_dynamics", lambda: lib.inverse_dynamics_device(d_x, d_qdd, N,
          ("rollout", lambda: lib.rollout_device(d_x, d_u, N, 16, 1e-3, d_xT=d_xT, stride_x0=3 * n, stream=st)),  # 16 steps, final state only: us_per_launch / 16 is one step
          ("rollout_linearized", lambda: lib.rollout_linearized_device(d_x, d_u, N, 16, 1e-3, d_xT=d_xT, d_fx=d_fx16, d_fu=d_fu16, stride_x0=3 * n, stream=st)),  # 16 steps, fx + fu + final state: / 16 is one linearised step
          ("rollout_adjoint", lambda: lib.rollout_adjoint_device(d_tr16, d_u, N, 16, 1e-3, d_gx=d_g16, d_grad_x0=d_gx0, d_grad_u=d_gu16, stream=st)),  # 16 reverse steps, grad_x0 + grad_u: / 16 is one adjoint step
+         ("rollout_feedback", lambda: lib.rollout_feedback_device(d_x, d_u, d_K16, d_tr16, N, 16, 1e-3, d_xT=d_xT, d_u_out=d_gu16, stride_x0=3 * n, stream=st)),  # 16 closed-loop steps, dense K, u_out + final state: / 16 is one step
          ("forward_dynamics_gradient", lambda: lib.forward_dynamics_gradient_device(d_x, N, d_g, stream=st))]
 t_end = time.perf_counter() + 0.15
 while time.perf_counter() < t_end:
