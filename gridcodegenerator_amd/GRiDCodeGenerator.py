@@ -10,9 +10,15 @@ wave64 hardware instead of CUDA:
 ``robot`` is any object offering the URDFParser-style getters; gridcodegenerator_amd.robot
 provides one (RobotModel) for JSON/URDF descriptions.
 """
+import os
+import shutil
+
 import numpy as np
 
 from .robot import DuckRobot
+
+# the hand-written device header every generated <namespace>.cuh includes (kernel shell: input staging, constants, copy-out)
+SHELL_HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "grid_kernel_shell.h")
 
 # Generation-time tuning knobs.  They are reachable ONLY through the constructor (``GRiDCodeGenerator(robot, tuning={...})``): nothing in
 # the process environment changes the generated code.  The "ablation" group emits kernels whose RESULTS ARE WRONG on purpose (timing
@@ -70,6 +76,10 @@ TUNING_DEFAULTS = {
     "composite_scan": "f32",    # f32 | f64: precision of the suffix sums of the link inertias (tip/branch-frame paths); f64 = exact sums, rounded once
     "adjoint_prefetch": "auto", # auto | True | False: rollout_adjoint_kernel requests g_t and the row of step t-1 before the dynamics of step t (five registers live across it) or
                                 # loads them after it; auto = before, except for 32-lane and wider lane groups (algorithms/_rollout_adjoint.py: gen_rollout_adjoint_prefetch)
+    "shell": "inputs,qreg,store",  # forward_dynamics_gradient kernel (u input) of tip-frame robots: which parts of its shell are the hand-written functions of
+                                # include/grid_kernel_shell.h - inputs (branch-free staging), qreg (sin/cos takes q from the load's register), store (straight-line
+                                # copy-out of full waves); measured slower and left out: consts (the lane's constant rows requested IN FRONT of
+                                # the input loads instead of behind them), chain (select-free frame chain); "" = the emitted shell of the other kernels
     "base_origin": "auto",      # auto | off | <joint position>: tip-frame path - the joint-space inertia entries of the base half of a chain are
                                 # evaluated about the origin of this joint instead of the tip (fp32 accuracy); auto = L // 2 for L >= 5
 }
@@ -102,6 +112,9 @@ def resolve_tuning(tuning=None, COLS_PER_LANE=None):
         raise ValueError("tuning['gradient_walk'] must be auto, registers, lds, tipframe or branch")
     if t["cols_per_lane"] not in (1, 2):
         raise ValueError("tuning['cols_per_lane'] must be 1 or 2")
+    t["shell"] = tuple(sorted(set(x for x in str(t["shell"] or "").replace(" ", "").split(",") if x)))
+    if any(x not in ("inputs", "qreg", "consts", "store", "chain") for x in t["shell"]) or ("qreg" in t["shell"] and "inputs" not in t["shell"]):
+        raise ValueError("tuning['shell'] is a comma-separated subset of inputs, qreg, consts, store, chain (qreg needs inputs)")
     if t["tip_chain"] not in ("select", "lds"):
         raise ValueError("tuning['tip_chain'] must be select or lds")
     if t["so_origin"] not in ("joint", "base"):
@@ -140,7 +153,7 @@ class GRiDCodeGenerator:
         gen_forward_dynamics_gradient_inner_python, gen_forward_dynamics_gradient_device, gen_forward_dynamics_gradient_stream_device, gen_forward_dynamics_gradient_kernel, \
         gen_forward_dynamics_gradient_host, gen_forward_dynamics_gradient, gen_forward_dynamics_gradient_device_function_call, \
         gen_tip_frame_link_constants, gen_tip_frame_joint_offset, gen_tip_frame_library, gen_forward_dynamics_gradient_inner_tip, \
-        gen_forward_dynamics_gradient_inner_tip_function_call, gen_tip_frame_gradient, gen_tip_frame_fused_so, \
+        gen_forward_dynamics_gradient_inner_tip_function_call, gen_tip_frame_gradient, gen_tip_frame_fused_so, gen_kernel_shell, \
         gen_inverse_dynamics_inner_tip, gen_inverse_dynamics_gradient_inner_tip, gen_forward_dynamics_inner_tip, gen_direct_minv_inner_tip, gen_crba_inner_tip, gen_tip_frame_components, \
         gen_branch_frame_plan, gen_branch_frame_constants, gen_branch_frame_library, gen_branch_frame_components, gen_forward_dynamics_gradient_inner_branch, gen_forward_dynamics_gradient_inner_branch_stream, \
         gen_forward_dynamics_gradient_inner_branch_function_call
@@ -274,6 +287,7 @@ class GRiDCodeGenerator:
         self.gen_add_code_line("")
         self.gen_add_code_lines(["#include <assert.h>", "#include <stdio.h>", "#include <stdlib.h>", "#include <math.h>", "#include <time.h>",
                                  "#include <hip/hip_runtime.h>"])
+        self.gen_add_code_line('#include "grid_kernel_shell.h"  // hand-written kernel shell (a copy is written next to this file; the source is include/grid_kernel_shell.h)')
         self.gen_add_code_lines(["// single kernel timing helper code",
                                  "#define time_delta_us_timespec(start,end) (1e6*static_cast<double>(end.tv_sec - start.tv_sec)+1e-3*static_cast<double>(end.tv_nsec - start.tv_nsec))"])
         self.gen_add_code_line("")
@@ -685,4 +699,5 @@ class GRiDCodeGenerator:
         self.gen_add_end_control_flow()
         with open(self.file_namespace + ".cuh", "w") as f:
             f.write(self.code_str)
+        shutil.copyfile(SHELL_HEADER, os.path.basename(SHELL_HEADER))  # (the generated header includes it: it travels with it)
         return self.code_str

@@ -135,6 +135,58 @@ def gen_forward_dynamics_gradient_stream_device(self, use_thread_group=False):
     self.gen_add_end_function()
 
 
+def _gen_shell_kernel_body(self, shell, use_thread_group=False):
+    """One trip of the batch loop of the u-input kernel of a tip-frame robot behind the hand-written shell of include/grid_kernel_shell.h (shell: which of
+    its parts, tuning "shell"; the parts left out are the emitted ones).  The wave's path is serial, so the head keeps ONE exposed memory wait - the lane's
+    constant rows and its inputs are in flight together, the sin/cos starts from the load's register - and the tail of a full wave reads its whole staging
+    area, waits once and stores back to back.  Same arithmetic as forward_dynamics_gradient_device: load_update_XImats_helpers, the tip-frame inner."""
+    n = self.model.n
+    L, nseg = self.tip_L, self.tip_nseg
+    A = self.gen_add_code_line
+    tab = "grid_model_constants(static_cast<const T *>(nullptr))"
+
+    def load_constants():
+        A("T XT[18], Lc[12]%s; // this lane's rows of the constant table: X_tree of its joint, its link constants%s" % ((", Rj[%d]" % (4 * L), ", the joint offsets of its chain") if nseg > 1 else ("", "")))
+        A("grid_shell_load_constants<18>(XT, &%s[18*((lane < %d) ? lane : %d)]);" % (tab, n, n - 1))
+        A("grid_shell_load_constants<12>(Lc, &%s[%d + 12*lane]);" % (tab, 54 * n))
+        if nseg > 1:
+            A("grid_shell_load_constants<%d>(Rj, &%s[%d + 4*%d*((lane / %d < %d) ? lane / %d : %d)]);" % (4 * L, tab, 54 * n + 12 * self.lanes_per_solve, L, L, nseg, L, nseg - 1))
+
+    if "consts" in shell:
+        A("// head: the lane's constant rows and its inputs are in flight together (one exposed memory wait)")
+        load_constants()
+    if "inputs" in shell:
+        A("const T q_in = grid_shell_load_inputs<T, %d, GRID_LANES_PER_SOLVE>(s_q_qd_u, &d_q_qd_u[static_cast<size_t>(kc)*stride_q_qd_u], lane);" % (3 * n))
+        if "qreg" in shell:
+            A("const T q_lane = q_in; // (element `lane` of the record: q of the lane's own joint - no LDS round trip in front of the sin/cos)")
+        else:
+            self.gen_add_sync(use_thread_group)
+            A("const T q_lane = s_q[lane]; (void)q_in;")
+    else:
+        self.gen_kernel_load_inputs("q_qd_u", "stride_q_qd_u", 3 * n, use_thread_group)
+        A("const T q_lane = s_q[lane];")
+    if "consts" not in shell:
+        load_constants()
+    A("// compute")
+    A("T *s_X = &s_mem[GRID_OFF_X]; T *s_U = &s_mem[GRID_OFF_U];")
+    A("load_update_XImats_helpers_regs<T>(s_X, q_lane, XT, lane);")
+    self.gen_add_sync(use_thread_group)
+    A("forward_dynamics_gradient_inner_tip_shell<T>(s_df_du, s_qd, s_u, s_X, s_U, s_Minv, Lc, %sgravity, lane); // hand-off records in the U|T scratch, M in the M^-1 slot" % ("Rj, " if nseg > 1 else ""))
+    if "store" not in shell:
+        self.gen_kernel_save_result("df_du", 2 * n * n, 2 * n * n, use_thread_group)
+        return
+    self.gen_add_sync(use_thread_group)
+    A("// save down to global: wave-cooperative, coalesced; what the copy-out branches on is wave-uniform")
+    A("{", True)
+    self.gen_add_code_lines(["const int wave0 = grid_shell_wave_uniform(tid & ~63); // first thread of this wave",
+                             "const int gw0 = wave0 / GRID_LANES_PER_SOLVE, kw = k0 + gw0; // first lane group of this wave, its solve",
+                             "int nv = NUM_TIMESTEPS_OUT - kw; { const int ng = gpb - gw0; nv = nv < ng ? nv : ng; nv = nv < GRID_SOLVES_PER_WAVE ? nv : GRID_SOLVES_PER_WAVE; nv = nv > 0 ? nv : 0; } // (a wave whose lane groups are all past the end of the batch writes nothing)",
+                             "int wn = gpb*GRID_LANES_PER_SOLVE - wave0; wn = wn < 64 ? wn : 64; // lanes of this wave that take part (the last wave of a block may be partial)",
+                             "grid_shell_store_record<T, %d, GRID_SOLVES_PER_WAVE, %s>(&d_df_du[static_cast<size_t>(kw)*%d], &s_out_all[gw0*%d], nv, wn, tid & 63);" % (2 * n * n, "true" if self.tuning["nt_store"] else "false", 2 * n * n, 2 * n * n)])
+    self.gen_add_end_control_flow()
+    self.gen_add_sync(use_thread_group)
+
+
 def gen_forward_dynamics_gradient_kernel(self, use_thread_group=False, use_qdd_Minv_input=False, single_call_timing=False):
     n = self.model.n
     stream = getattr(self, "fd_stream_out", False) and not use_qdd_Minv_input and not single_call_timing
@@ -180,6 +232,12 @@ def gen_forward_dynamics_gradient_kernel(self, use_thread_group=False, use_qdd_M
         self.gen_add_code_line("if (!valid) {return;}")
     else:
         self.gen_add_parallel_loop("k", "NUM_TIMESTEPS", use_thread_group, block_level=True)
+    shell = () if (use_qdd_Minv_input or single_call_timing or stream) else self.gen_kernel_shell()
+    if shell:
+        _gen_shell_kernel_body(self, shell, use_thread_group)
+        self.gen_add_end_control_flow()
+        self.gen_add_end_function()
+        return
     if use_qdd_Minv_input:
         self.gen_kernel_load_inputs("q_qd", "stride_q_qd", 2 * n, use_thread_group, "qdd", n, n, "Minv", n * n, n * n, symmetrize3=n)
     else:

@@ -226,10 +226,58 @@ def _probe(self, stage, *arrays):
         self.gen_add_code_line("for (int r = 0; r < %s; r++) { %s[r] = static_cast<T>(static_cast<float>(%s[r])); } // round_probe %s" % (ln, nm, nm, stage))
 
 
-def _chain_step(self, i, s_F=None, with_gravity=True, base_family=False):
+def _chain_step_in_place(self, i, with_gravity, base_family, rj_regs):
+    """Select-free form of _chain_step (tuning shell "chain"): the chain is monotone - a lane needs the running frame up to its own joint and nothing
+    after - so every lane advances ITS OWN (myR, myp) while pos < i and simply stops; the same products in the same order as the wave-uniform chain,
+    no select.  What every lane needs of the whole chain (gvec, pB) is then read from the chain's first lane, the one that ran all of it."""
+    m = self.model
+    L, nseg = self.tip_L, self.tip_nseg
+    E_nz = m.X_pattern[i][0].copy()
+    for sgi in range(1, nseg):
+        E_nz |= m.X_pattern[sgi * L + i][0]
+    C = lambda x: "static_cast<T>(" + repr(float(x)) + ")"
+    J = str(i) if nseg == 1 else "(base + %d)" % i
+    self.gen_add_code_line("{ // tip-frame chain, position %d: lanes of joints nearer the base move their frame on to the parent of that joint" % i, True)
+    if base_family and self.tip_jB is not None and i == self.tip_jB:
+        self.gen_add_code_line("pB[0] = grid_group_shfl(myp[0], base); pB[1] = grid_group_shfl(myp[1], base); pB[2] = grid_group_shfl(myp[2], base); // origin of the base family: the frame origin of the joint at position %d (the chain's first lane is there now)" % i)
+    self.gen_add_code_line("const T *Ei = &s_X[GRID_X_STRIDE*%s]; // E(q) of that joint: parent -> child coordinates (row-major)" % J)
+    self.gen_add_code_line("T Rn[9];")
+    for rr in range(3):
+        for cc in range(3):
+            terms = ["myR[%d]*Ei[%d]" % (3 * rr + k, 3 * k + cc) for k in range(3) if E_nz[k, cc]]
+            self.gen_add_code_line("Rn[%d] = %s;" % (3 * rr + cc, " + ".join(terms) if terms else "static_cast<T>(0)"))
+    if i > 0:
+        self.gen_add_code_line("if (pos < %d) {" % i, True)
+        if nseg == 1:
+            r = self.gen_tip_frame_joint_offset(i)
+            for rr in range(3):
+                terms = ["Rn[%d]*%s" % (3 * rr + k, C(r[k])) for k in range(3) if r[k] != 0.0]
+                if terms:
+                    self.gen_add_code_line("myp[%d] -= %s;" % (rr, " + ".join(terms)))
+        else:
+            if rj_regs:
+                self.gen_add_code_line("const T *rj = &Rj[%d]; // origin of that joint's frame in its parent's coordinates" % (4 * i))
+            else:
+                self.gen_add_code_line("const T *rj = &grid_model_constants(static_cast<const T *>(nullptr))[%d + 4*%s]; // origin of that joint's frame in its parent's coordinates" % (54 * m.n + 12 * self.lanes_per_solve, J))
+            self.gen_add_code_line("#pragma unroll")
+            self.gen_add_code_line("for (int r = 0; r < 3; r++) { myp[r] -= Rn[3*r]*rj[0] + Rn[3*r+1]*rj[1] + Rn[3*r+2]*rj[2]; }")
+        self.gen_add_code_line("#pragma unroll")
+        self.gen_add_code_line("for (int r = 0; r < 9; r++) { myR[r] = Rn[r]; }")
+        self.gen_add_end_control_flow()
+    elif with_gravity:
+        self.gen_add_code_line("gvec[0] = gravity*grid_group_shfl(Rn[2], base); gvec[1] = gravity*grid_group_shfl(Rn[5], base); gvec[2] = gravity*grid_group_shfl(Rn[8], base); // base acceleration (0,0,g) in F coordinates, from the lane that ran the whole chain")
+    else:
+        self.gen_add_code_line("(void)Rn; gvec[0] = gvec[1] = gvec[2] = static_cast<T>(0);")
+    self.gen_add_end_control_flow()
+
+
+def _chain_step(self, i, s_F=None, with_gravity=True, base_family=False, rj_regs=False, in_place=False):
     """Frame-chain step of the joint at position i of every chain: hand (R, p) to the lane that owns that joint, then move the running
     frame to the parent (or, for the root, read off the world's gravity direction).  The hand-off is a register select on every lane
-    (s_F None) or one LDS record per joint written by lane 0 and read back by its owner after the chain (single chains only)."""
+    (s_F None) or one LDS record per joint written by lane 0 and read back by its owner after the chain (single chains only).
+    rj_regs: forests read the joint offsets from the register array Rj (loaded at the head of the kernel) instead of the constant table."""
+    if in_place and s_F is None:
+        return _chain_step_in_place(self, i, with_gravity, base_family, rj_regs)
     m = self.model
     L, nseg = self.tip_L, self.tip_nseg
     E_nz = m.X_pattern[i][0].copy()
@@ -265,7 +313,10 @@ def _chain_step(self, i, s_F=None, with_gravity=True, base_family=False):
                 if terms:
                     self.gen_add_code_line("pc[%d] -= %s;" % (rr, " + ".join(terms)))
         else:
-            self.gen_add_code_line("const T *rj = &grid_model_constants(static_cast<const T *>(nullptr))[%d + 4*%s]; // origin of that joint's frame in its parent's coordinates" % (54 * m.n + 12 * self.lanes_per_solve, J))
+            if rj_regs:
+                self.gen_add_code_line("const T *rj = &Rj[%d]; // origin of that joint's frame in its parent's coordinates" % (4 * i))
+            else:
+                self.gen_add_code_line("const T *rj = &grid_model_constants(static_cast<const T *>(nullptr))[%d + 4*%s]; // origin of that joint's frame in its parent's coordinates" % (54 * m.n + 12 * self.lanes_per_solve, J))
             self.gen_add_code_line("#pragma unroll")
             self.gen_add_code_line("for (int r = 0; r < 3; r++) { pc[r] -= Rn[3*r]*rj[0] + Rn[3*r+1]*rj[1] + Rn[3*r+2]*rj[2]; }")
         self.gen_add_code_line("#pragma unroll")
@@ -504,12 +555,14 @@ def _emit_assembly(self, s_G="s_G", dst="s_df_du", minv="s_Minv"):
     self.gen_add_end_control_flow()
 
 
-def _emit_link_constants_load(self):
+def _emit_link_constants_load(self, from_regs=False):
+    """from_regs: Lc is a parameter of the function (the kernel shell loaded the lane's row at the head of the kernel)."""
     n = self.model.n
-    self.gen_add_code_line("T Lc[12]; // this lane's link constants: Ic (6, about the centre of mass), c (3), m, damping, axis")
-    self.gen_add_code_line("{ const T *d_L = &grid_model_constants(static_cast<const T *>(nullptr))[%d + 12*lane]; (void)d_robotModel;" % (54 * n))
-    self.gen_add_code_line("  #pragma unroll")
-    self.gen_add_code_line("  for (int r = 0; r < 12; r++) { Lc[r] = d_L[r]; } }")
+    if not from_regs:
+        self.gen_add_code_line("T Lc[12]; // this lane's link constants: Ic (6, about the centre of mass), c (3), m, damping, axis")
+        self.gen_add_code_line("{ const T *d_L = &grid_model_constants(static_cast<const T *>(nullptr))[%d + 12*lane]; (void)d_robotModel;" % (54 * n))
+        self.gen_add_code_line("  #pragma unroll")
+        self.gen_add_code_line("  for (int r = 0; r < 12; r++) { Lc[r] = d_L[r]; } }")
     L, nseg = self.tip_L, self.tip_nseg
     if nseg == 1:
         self.gen_add_code_line("const int base = 0, pos = lane; // one chain: position in the chain == lane")
@@ -544,8 +597,12 @@ def _emit_ldl_solve(self, b, U="Uf", rd="rd"):
         self.gen_add_code_line("%s[%d] -= %s;" % (b, k, " + ".join("%s%d_%d*%s[%d]" % (U, i, k, b, i) for i in range(k))))
 
 
-def gen_forward_dynamics_gradient_inner_tip(self, use_thread_group=False, use_qdd_Minv_input=False, with_so=False):
+def gen_forward_dynamics_gradient_inner_tip(self, use_thread_group=False, use_qdd_Minv_input=False, with_so=False, shell=None):
     """The fused inner of the tip-frame path.
+    shell (u-input form only; a tuple of tuning "shell" items): forward_dynamics_gradient_inner_tip_shell - what the forward_dynamics_gradient kernel itself
+    calls behind the hand-written shell of include/grid_kernel_shell.h.  The lane's link constants Lc (forests: and the joint offsets Rj of its chain) are
+    parameters - the kernel loaded them at its head, next to the inputs - so no model constant is read behind the kernel's first fence; with "chain" in
+    shell the frame chain is the select-free form (_chain_step_in_place).  Same arithmetic, same bits.
     with_so (u-input form only): forward_dynamics_gradient_inner_tip_so - what fdsva_so runs.  At the end of the gradient every per-joint quantity the
     second-order inverse-dynamics derivatives are built from is in this lane's registers, evaluated at qdd = FD(q, qd, u): S, Pd, Pdd, the composites
     I^C, B^C and t1..t4 (= T1, T4, T3, -T2 of algorithms/_idsva_so.py); the function goes straight on to the idsva_so main loops instead of
@@ -556,8 +613,8 @@ def gen_forward_dynamics_gradient_inner_tip(self, use_thread_group=False, use_qd
     of dc/du.  No link-local transforms, no articulated inertias, no M^-1 sweeps."""
     m = self.model
     n = m.n
-    assert not (with_so and use_qdd_Minv_input)
-    name = "forward_dynamics_gradient_inner_tip" + ("_qdd_minv" if use_qdd_Minv_input else "") + ("_so" if with_so else "")
+    assert not (with_so and use_qdd_Minv_input) and not (shell is not None and (with_so or use_qdd_Minv_input))
+    name = "forward_dynamics_gradient_inner_tip" + ("_qdd_minv" if use_qdd_Minv_input else "") + ("_so" if with_so else "") + ("_shell" if shell is not None else "")
     notes = ["serial revolute chains only; all link quantities are expressed in the frame of the tip link (see the module notes of",
              "algorithms/_tip_frame_gradient.py); same results as direct_minv_inner + inverse_dynamics_inner + inverse_dynamics_gradient_inner",
              "s_df_du receives -Minv*dc/du in the device layout [col*n + row]; the caller must grid_wave_sync() before other lanes read it"]
@@ -578,8 +635,14 @@ def gen_forward_dynamics_gradient_inner_tip(self, use_thread_group=False, use_qd
                        "active is false for lane groups without a solve (they compute but do not store through so)"]
             params += ["s_rec is LDS for the per-joint records [S | Pd | Pdd] of the second-order loops, 20 values per joint (may be s_X)"]
             sig = sig.replace(" = nullptr", "") + ", T *so, T *s_rec, const bool active"  # (no __restrict__: so may overlap the gradient's dead working set)
-    params += ["d_robotModel is the pointer to the initialized model specific helpers on the GPU", "gravity is the gravity constant",
-               "lane is the caller's lane index inside the solve's lane group"]
+    if shell is not None:
+        sig = sig.replace("const robotModel<T> *d_robotModel", "const T (&Lc)[12]" + (", const T (&Rj)[%d]" % (4 * self.tip_L) if self.tip_nseg > 1 else ""))
+        params += ["Lc is this lane's row of link constants (gen_tip_frame_link_constants), loaded by the caller"]
+        if self.tip_nseg > 1:
+            params += ["Rj is the joint-offset table of this lane's chain (4 values per joint), loaded by the caller"]
+    else:
+        params += ["d_robotModel is the pointer to the initialized model specific helpers on the GPU"]
+    params += ["gravity is the gravity constant", "lane is the caller's lane index inside the solve's lane group"]
     self.gen_add_func_doc("Computes the gradient of forward dynamics in the tip frame", notes, params, None)
     self.gen_add_code_line("template <typename T>")
     self.gen_add_code_line("__device__ __forceinline__")
@@ -593,7 +656,7 @@ def gen_forward_dynamics_gradient_inner_tip(self, use_thread_group=False, use_qd
     if ts_mode:
         self.gen_add_code_line("unsigned long long grid_ts[8];")
     TS(0)
-    _emit_link_constants_load(self)
+    _emit_link_constants_load(self, from_regs=shell is not None)
     _emit_chain_decls(self)
     chain_lds = (not use_qdd_Minv_input) and self.tip_nseg == 1 and self.tuning["tip_chain"] == "lds"
     L = self.tip_L
@@ -603,7 +666,7 @@ def gen_forward_dynamics_gradient_inner_tip(self, use_thread_group=False, use_qd
         self.gen_add_code_line("gvec[0] = gvec[1] = static_cast<T>(0); gvec[2] = gravity; // (ablation: every frame is the identity)")
     else:
         for i in range(L - 1, -1, -1):
-            _chain_step(self, i, "s_G" if chain_lds else None, base_family=bf)
+            _chain_step(self, i, "s_G" if chain_lds else None, base_family=bf, rj_regs=shell is not None, in_place=shell is not None and "chain" in shell)
     if chain_lds:
         self.gen_add_sync(use_thread_group)
         self.gen_add_code_line("if (lane < %d) { // this lane's own frame (lanes without a joint keep the identity; their link constants are zero)" % (n - 1), True)
@@ -1025,8 +1088,18 @@ def gen_tip_frame_fused_so(self):
                 and self.tuning["so_mapping"] == "balanced" and self.tuning["so_loops"] == "dots" and int(self.tuning["debug_stop"]) in (0, 30, 31, 32))
 
 
+def gen_kernel_shell(self):
+    """The parts of the forward_dynamics_gradient kernel's shell (u input) that are the hand-written functions of include/grid_kernel_shell.h (tuning "shell");
+    empty where the kernel keeps the emitted shell: robots off the tip-frame path and the timing-ablation builds."""
+    if not (self.tip_frame and not getattr(self, "branch_frame", False)) or int(self.tuning["debug_stop"]) != 0 or self.tuning["no_store"]:
+        return ()
+    return tuple(self.tuning["shell"])
+
+
 def gen_tip_frame_gradient(self, use_thread_group=False):
     self.gen_forward_dynamics_gradient_inner_tip(use_thread_group, False)
+    if self.gen_kernel_shell():
+        self.gen_forward_dynamics_gradient_inner_tip(use_thread_group, False, shell=self.gen_kernel_shell())
     self.gen_forward_dynamics_gradient_inner_tip(use_thread_group, True)
     if self.gen_tip_frame_fused_so():
         self.gen_forward_dynamics_gradient_inner_tip(use_thread_group, False, with_so=True)

@@ -285,21 +285,39 @@ def gen_load_update_XImats_helpers(self, use_thread_group=False):
         "    *c = ((q + 1) & 2) ? -b : b;",
         "}",
         "__device__ __forceinline__ void grid_sincos(const double x, double *s, double *c) { sincos(x, s, c); }", ""])
-    self.gen_add_func_doc("Updates the joint transforms X(q) of one solve in LDS",
+    _emit_update_X(self, False)
+    _emit_update_X(self, True)
+
+
+def _emit_update_X(self, from_regs):
+    """load_update_XImats_helpers, or (from_regs) its form for a kernel shell that already holds q of the lane's joint and the lane's X_tree row in
+    registers (include/grid_kernel_shell.h: loaded at the head of the kernel) - the same arithmetic, no LDS read and no table read in front of it."""
+    m = self.model
+    n = m.n
+    self.gen_add_func_doc("Updates the joint transforms X(q) of one solve in LDS" + (" from registers" if from_regs else ""),
                           ["lane j of the solve's lane group handles joint j; only the rows of E and B that the joint motion mixes are",
                            "recomputed (12 of 18 numbers per joint), the remaining row is copied from the constant table"],
-                          ["s_X is this solve's compact transform storage (GRID_X_STRIDE floats per joint)",
-                           "s_q is the vector of joint positions in LDS",
-                           "d_robotModel is the pointer to the initialized model specific helpers on the GPU",
-                           "lane is the caller's lane index inside the solve's lane group"], None)
+                          ["s_X is this solve's compact transform storage (GRID_X_STRIDE floats per joint)"] +
+                          (["q is the position of the lane's own joint", "XT is the lane's row of the constant table: X_tree of its joint, [E(9)|B(9)]"] if from_regs else
+                           ["s_q is the vector of joint positions in LDS", "d_robotModel is the pointer to the initialized model specific helpers on the GPU"]) +
+                          ["lane is the caller's lane index inside the solve's lane group"], None)
     self.gen_add_code_line("template <typename T>")
     self.gen_add_code_line("__device__ __forceinline__")
-    self.gen_add_code_line("void load_update_XImats_helpers(T *s_X, const T *s_q, const robotModel<T> *d_robotModel, const int lane) {", True)
-    self.gen_add_code_line("if (lane < " + str(n) + ") {", True)
-    self.gen_add_code_lines(["const T *XT = &grid_model_constants(static_cast<const T *>(nullptr))[18*lane]; (void)d_robotModel;",
-                             "T *Xo = &s_X[GRID_X_STRIDE*lane];",
-                             "const T q = s_q[lane];"])
     types = sorted(set(m.S_index))
+    in_regs = from_regs and len(types) == 1  # one joint type: every lane evaluates its transform in registers and the lanes with a joint store it
+    if from_regs:
+        # (XT is in flight when this is entered.  Inside an `if (lane < n)` the compiler sinks the loads of XT into the block, behind the wait of whatever was
+        #  stored in front of it; used by unconditional arithmetic they stay where the caller issued them.  Several joint types: the lane-mask tests of the
+        #  types exclude the lanes without a joint and every type's block uses XT.)
+        self.gen_add_code_line("void load_update_XImats_helpers_regs(T *s_X, const T q, const T (&XT)[18], const int lane) {", True)
+        self.gen_add_code_line("{", True)
+        self.gen_add_code_line("T Xo[18];" if in_regs else "T *Xo = &s_X[GRID_X_STRIDE*lane];")
+    else:
+        self.gen_add_code_line("void load_update_XImats_helpers(T *s_X, const T *s_q, const robotModel<T> *d_robotModel, const int lane) {", True)
+        self.gen_add_code_line("if (lane < " + str(n) + ") {", True)
+        self.gen_add_code_lines(["const T *XT = &grid_model_constants(static_cast<const T *>(nullptr))[18*lane]; (void)d_robotModel;",
+                                 "T *Xo = &s_X[GRID_X_STRIDE*lane];",
+                                 "const T q = s_q[lane];"])
     if len(types) > 1 and any(s_ < 3 for s_ in types):  # one sine/cosine for all revolute lanes instead of one per axis block (the blocks run one after the other)
         self.gen_add_code_line("T sn, cs; grid_sincos(q, &sn, &cs);")
     first = True
@@ -329,6 +347,13 @@ def gen_load_update_XImats_helpers(self, use_thread_group=False):
             self.gen_add_code_line("Xo[%d+c] = XT[%d+c] - q*XT[%d+c];" % (9 + 3 * r2, 9 + 3 * r2, 3 * r1))
             self.gen_add_code_line("Xo[%d+c] = XT[%d+c];" % (9 + 3 * a, 9 + 3 * a))
             self.gen_add_end_control_flow()
+        self.gen_add_end_control_flow()
+    if in_regs:
+        self.gen_add_code_line("#pragma unroll")
+        self.gen_add_code_line("for (int c = 0; c < 18; c++) { grid_pin(Xo[c]); } // (keeps the arithmetic out of the store block below)")
+        self.gen_add_code_line("if (lane < " + str(n) + ") {", True)
+        self.gen_add_code_line("#pragma unroll")
+        self.gen_add_code_line("for (int c = 0; c < 18; c++) { s_X[GRID_X_STRIDE*lane + c] = Xo[c]; }")
         self.gen_add_end_control_flow()
     self.gen_add_end_control_flow()
     self.gen_add_end_function()

@@ -57,8 +57,7 @@ def build_library(robot, build_dir=None, force=False, extra_flags=(), verbose=Fa
     so = library_path(name, build_dir)
     header = generate_header(robot, out_dir, cols_per_lane=cols_per_lane, tuning=tuning)
     stamp = so + ".stamp"
-    srcs_mtime = max(os.path.getmtime(p) for p in (header, CAPI_SRC, os.path.join(INCLUDE_DIR, "grid_capi.h")))
-    sig = open(header).read() + open(CAPI_SRC).read() + " ".join(HIPCC_FLAGS + list(extra_flags))
+    sig = open(header).read() + open(os.path.join(INCLUDE_DIR, "grid_kernel_shell.h")).read() + open(CAPI_SRC).read() + " ".join(HIPCC_FLAGS + list(extra_flags))
     import hashlib
     digest = hashlib.sha256(sig.encode()).hexdigest()
     if not force and os.path.exists(so) and os.path.exists(stamp) and open(stamp).read() == digest:
